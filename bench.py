@@ -29,6 +29,7 @@ The key is a VALID key (fk_setup*, fixed toxic waste), so the proof produced in 
 with the Groth16 pairing equation.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR      (also writes the last timed proof as DIR/proof.npy)
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks: torch.distributed.run as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -758,6 +759,13 @@ def check_digest(copies, two_witnesses, zs, want):
                   'compared in every run' % (e.get('threads'), e.get('oracle_seconds'))}
 
 
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the proof the last timed step handed back (fk_prove_r1cs_wait: 256 Borsh bytes a || b || c) as DIR/proof.npy, one
+    float64 per byte (exact).  The proof is a function of (key, system, witness, r, s) alone, all fixed by the arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'proof.npy'), np.frombuffer(bytes(proof), dtype=np.uint8).astype(np.float64))
+
+
 def self_launch(n_gpus):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py <same
     arguments>` as a child process (one rank per GPU, rendezvous on 127.0.0.1 at a free port), pass its output through and
@@ -834,7 +842,12 @@ def main():
                          'committed pass under profiles/.  auto: on for systems of 2^23 rows and more (the benchmark), off for small ones; skipped with the reason when '
                          'rocprofv3 is absent or --max-seconds would be exceeded')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend ('nccl' = RCCL; 'gloo' only for single-GPU dry runs of the N>1 code path with FK_BENCH_SAME_DEVICE=1)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned to its caller (the 256 proof bytes) as DIR/proof.npy, float64; '
+                         'the inputs are fixed by the arguments, so two builds can be compared output for output')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, as fresh child processes, BEFORE this process has
@@ -1191,6 +1204,8 @@ def main():
         raise AssertionError('bench: proofs differ between steps (non-deterministic result)')
     if two_witnesses and want[1] is not None and want[1] == want[0]:
         raise AssertionError('bench: two different witnesses gave the same proof bytes')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proofs[-1])
     if multi:
         import torch.distributed as dist
         tmax = torch.tensor([elapsed], dtype=torch.float64)

@@ -148,3 +148,15 @@ def eddsa_batch_inputs(copies=4096):
     z = np.ascontiguousarray(np.concatenate([zs[0][:1]] + [zs[p][1:ni] for p in picks] + [zs[p][ni:] for p in picks]))
     r, s = fx.mont_fr(rnd.randrange(ref.R)), fx.mont_fr(rnd.randrange(ref.R))
     return sigs, one, picks, z, r, s
+
+
+def visible_gpu_count():
+    """The GPUs a process started from here sees, counted in a short-lived child process.  Not in the test process itself: torch
+    bundles its own HIP and HSA runtimes, and once they are initialised beside the ones libfawkes_hip.so and librccl load, an
+    in-process RCCL communicator finds no device (tests/test_gpu_multi.py, transport rccl)."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, '-c', 'import torch; print(torch.cuda.device_count())'], capture_output=True, text=True, timeout=300)
+    if out.returncode != 0 or not out.stdout.strip():
+        raise RuntimeError('counting GPUs in a child process failed (rc %d): %s' % (out.returncode, (out.stdout + out.stderr)[-1000:]))
+    return int(out.stdout.strip().splitlines()[-1])

@@ -27,9 +27,9 @@ def test_library_exports_header_symbols():
 
 def test_no_gpu_fails_loudly():
     """There is no CPU fallback: without a HIP device the context cannot be created."""
-    import torch
     import fawkes_crypto_amd as fk
-    if torch.cuda.device_count() > 0:
+    from helpers import visible_gpu_count
+    if visible_gpu_count() > 0:
         pytest.skip('a GPU is visible')
     with pytest.raises(fk.FkError):
         fk.Context(0)

@@ -63,3 +63,14 @@ def test_timed_proofs_are_compared_with_the_committed_oracle_bytes():
     assert bench.check_digest(None, False, None, want) is None         # synthetic workload
     other = bench.check_digest(1741, True, inst_zs[:3], want)           # another witness set: the entry does not apply, and says why
     assert other['applies'] is False and 'another set' in other['why']
+
+
+def test_dump_outputs_writes_the_proof_bytes_exactly(tmp_path):
+    """--dump-outputs DIR: the 256 proof bytes of the last timed step as DIR/proof.npy, float64, one value per byte"""
+    import bench
+    proof = bytes(range(256))
+    out = tmp_path / 'nested' / 'dump'
+    bench.dump_outputs(str(out), np.frombuffer(proof, np.uint8))
+    got = np.load(out / 'proof.npy')
+    assert got.dtype == np.float64 and got.shape == (256,)
+    assert bytes(got.astype(np.uint8)) == proof and np.array_equal(got, np.arange(256, dtype=np.float64))

@@ -330,7 +330,9 @@ def _preflight_worker(rank, world, port, q):
 def test_preflight_two_ranks_gloo_no_gpu():
     """The preflight's host side with two ranks and NO GPU: each rank starts its child process, the children rendezvous over their own file store,
     agree on a verdict (gloo all-reduce) and every rank reads the same decision.  Backend gloo: RCCL is not exercised (and says so); rank 0's library
-    part fails for want of a device and is REPORTED, not raised -- the block must come back whatever happens in the child."""
+    part fails for want of a device and is REPORTED, not raised -- the block must come back whatever happens in the child.  Where a GPU is visible
+    the library part runs for real instead (one device named twice) and must pass."""
+    from helpers import visible_gpu_count
     import multiprocessing as mp
     mpc = mp.get_context('spawn')
     q = mpc.Queue()
@@ -349,8 +351,11 @@ def test_preflight_two_ranks_gloo_no_gpu():
         assert b['decision']['backend'] == 'gloo' and b['decision']['host_events'] is False and 'RCCL not exercised' in b['decision']['why']
         assert b['seconds'] > 0
     lib = res[0]['library']
-    assert lib is not None and lib['ok'] is False and 'error' in lib          # no GPU here: reported
-    assert res[1]['library'] is None
+    assert lib is not None and lib['devices'] == [0, 0] and res[1]['library'] is None, lib
+    if visible_gpu_count() > 0:
+        assert lib['ok'] is True and 'error' not in lib and all(v == 0 for row in lib['pull_status'] for v in row), lib
+    else:
+        assert lib['ok'] is False and 'error' in lib          # no GPU here: reported
 
 
 def test_preflight_child_that_dies_is_a_verdict_not_an_exception(tmp_path, monkeypatch):

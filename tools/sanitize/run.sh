@@ -2,7 +2,7 @@
 # Host sanitizers over the gate codec (see gatestream_harness.cpp).  usage: tools/sanitize/run.sh [thread|address]   (default: both)
 set -e
 cd "$(dirname "$0")/../.."
-out=/tmp/fk_sanitize; mkdir -p $out
+out=$(mktemp -d "${TMPDIR:-/tmp}/fk_sanitize.XXXXXX"); trap 'rm -rf "$out"' EXIT     # private per run: no directory another user or run owns
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 CXX=${CXX:-/opt/rocm/lib/llvm/bin/clang++}
 for san in ${1:-thread address}; do
