@@ -28,8 +28,16 @@ is NOT imported here).
 The key is a VALID key (fk_setup*, fixed toxic waste), so the proof produced in the timed region is checked afterwards
 with the Groth16 pairing equation.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1                          (the headline figure alone: set-up, warm-up, the timed steps, the line)
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR      (also writes the last timed proof as DIR/proof.npy)
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                   (everything described below beside `value`: some six minutes)
+
+A plain run does only what `value` needs.  It times the same steps on the same resident key and explicit system as a --full run, but does not write and
+decode the gate blob to get there (40 s + 13 s at the benchmark size): the key still goes through its bellman bytes (fk_key_write_bellman ->
+fk_key_load_bellman(checked) -> fk_key_derive_levels), the system is built on the host (materialise_rollup: the rows, variables and terms the blob decodes
+to) and loaded through fk_r1cs_load_coded, the loader fk_r1cs_load_gates ends in.  The `Parameters` image with its `load` block, the preflight of a
+single-GPU run, the oracle's digests, the pairing check, the CPU baseline, the latencies, the roofline's live calibration and PMC passes and every leg at
+another form, size or rank arrangement are behind --full.
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks: torch.distributed.run as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -694,7 +702,7 @@ def measure_traffic_leg(args, log_m, g1_points, g2_points, rows, limit_s):
     if exe is None:
         return None, 'rocprofv3 not found on this machine'
     tmp = tempfile.mkdtemp(prefix='fk_pmc_', dir='/tmp' if os.path.isdir('/tmp') else None)
-    base = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--no-untiled', '--no-standalone',
+    base = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '1', '--warmup', '0', '--full', '--no-cpu-baseline', '--no-untiled', '--no-standalone',
             '--no-other-sizes', '--no-preflight', '--measure-traffic', 'off', '--tiled-headline', '--workload', args.workload, '--copies', str(args.copies),
             '--log2n', str(args.log2n), '--lc-terms', str(args.lc_terms)]
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'FK_BENCH_REHEARSE')}
@@ -842,6 +850,12 @@ def main():
                          'committed pass under profiles/.  auto: on for systems of 2^23 rows and more (the benchmark), off for small ones; skipped with the reason when '
                          'rocprofv3 is absent or --max-seconds would be exceeded')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend ('nccl' = RCCL; 'gloo' only for single-GPU dry runs of the N>1 code path with FK_BENCH_SAME_DEVICE=1)")
+    ap.add_argument('--full', action='store_true',
+                    help='everything the benchmark measures or checks beside its headline figure: the set-up through a `Parameters` image with its `load` block, the '
+                         'first-contact preflight of a single-GPU run, device-resident and one-at-a-time latencies, witness sensitivity, the tiled / untiled form, '
+                         'standalone MSM / NTT figures, the live VALU calibration, the oracle digest and pairing checks, the CPU baseline, the legs at other sizes, '
+                         'the PMC traffic passes and, N > 1, the replica and one-call legs (each still has its own --no-... switch).  Without it a run sets up, warms '
+                         'up, times the steps, writes --dump-outputs and prints the line: same timed steps on the same resident key and system, same `value`')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned to its caller (the 256 proof bytes) as DIR/proof.npy, float64; '
                          'the inputs are fixed by the arguments, so two builds can be compared output for output')
@@ -864,6 +878,13 @@ def main():
     # quotient with one rank) on a single GPU -- a rehearsal of the N > 1 plumbing over real RCCL, not a benchmark mode
     rehearse = os.environ.get('FK_BENCH_REHEARSE') == '1'
     multi = world > 1 or rehearse
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else: every optional leg is off (the pairing check goes with the CPU baseline's
+        # oracle), and a single-GPU run, which has no collective to try out, starts no preflight child
+        args.no_cpu_baseline = args.no_replicas = args.no_single_process = args.no_untiled = args.no_standalone = args.no_other_sizes = True
+        args.measure_traffic = 'off'
+        if not multi:
+            args.no_preflight = True
     # ---------------------------------------------------------------- first contact (before this process touches the GPU): the proof's collectives at
     # their real sizes, the peer-access table and a verified pull per device pair, in a child process with a time limit.  A failure selects the
     # documented fallback for THIS run (gloo-staged exchanges / host-side event waits) and is reported, instead of ending the run.
@@ -1066,6 +1087,16 @@ def main():
             'load_parameters_seconds_rank0': t_l1 - t_l0, 'one_rank_at_a_time': same_dev_turns > 1,
             'write': {'gates_encode_seconds': tm_w.get('gates_encode_s'), 'key_write_seconds': tm_w.get('key_write_s')},
         }
+    lean_form = params_form and not multi and not args.full
+    if lean_form:
+        # a plain run builds the explicit system on the host WHILE the GPU generates and reloads the key (below); the generated key needs no
+        # fixed-base levels, it is only written out (FK_MSM_PRECOMP is read at every key load)
+        import threading
+        explicit = {}
+        th_explicit = threading.Thread(target=lambda: explicit.update(system=materialise_rollup(copies)))
+        th_explicit.start()
+        prev_precomp = os.environ.get('FK_MSM_PRECOMP')
+        os.environ['FK_MSM_PRECOMP'] = '0'
     if not (multi and params_form):
         for turn in range(same_dev_turns):
             if same_dev_turns == 1 or turn == rank:
@@ -1080,7 +1111,34 @@ def main():
     # is dropped, and the prover is set up again from the image alone: gate blob -> fk_gates_decode -> fk_r1cs_load_gates (every one of the
     # 1.64e9 terms explicit in HBM), bellman part -> fk_key_load_bellman(checked).  `value` is measured on THAT system.
     load_block = None
-    if params_form and not multi:
+    if lean_form:
+        # The SAME resident key and system as under --full, without the gate blob in between (writing it takes 40 s at the benchmark size, decoding it 13 s):
+        # the key goes through its bellman bytes as there (fk_key_write_bellman -> fk_key_load_bellman(checked) -> fk_key_derive_levels, the levels planned
+        # before the system is resident), and the explicit system -- the rows, variables and terms the blob decodes to -- goes from the host's arrays through
+        # fk_r1cs_load_coded, the loader fk_r1cs_load_gates ends in.  One proof before the pipeline starts, as after load_parameters.
+        if prev_precomp is None:
+            del os.environ['FK_MSM_PRECOMP']
+        else:
+            os.environ['FK_MSM_PRECOMP'] = prev_precomp
+        bellman = ctx.write_key_bellman(key, vk)
+        key.free(); dr.free()
+        key = dr = None
+        key, gamma_g2, ic = ctx.load_key_bellman(bellman, flags=fk.api.FK_KEY_CHECKED | fk.api.FK_KEY_NO_LEVELS)
+        del bellman
+        key.derive_levels()
+        if not np.array_equal(np.asarray(ic), np.asarray(vk['ic'])) or bytes(gamma_g2) != bytes(vk['gamma_g2']):
+            raise AssertionError('bench: the verifying key read back from the bellman bytes differs from the generated one')
+        th_explicit.join()
+        if 'system' not in explicit:
+            raise RuntimeError('bench: building the explicit system on the host failed')
+        dr = ctx.load_r1cs_coded(*explicit.pop('system'))
+        if key.levels_headroom() < 0:                      # (as load_parameters: the levels are planned again if they left the system no room)
+            key.derive_levels()
+        info = dr.info()
+        if (info['n_a'], info['n_b']) != (n_a, n_b):
+            raise AssertionError('bench: the explicit system has other A / B queries than the tiled one')
+        first_proof = ctx.prove_witness(key, dr, z_pin[0], r, s).tobytes()
+    if params_form and not multi and args.full:
         from fawkes_crypto_amd import params_io as pio
         tm_w, tm_r = {}, {}
         image = pio.store_parameters_dev(ctx, key, vk, r1cs, copies=copies, quality=args.blob_quality, lgwin=22, timings=tm_w)
@@ -1213,10 +1271,13 @@ def main():
         elapsed = float(tmax.item())
 
     # ---- not `value`: the same proof with the witness already resident in HBM
-    d_z0 = ctx.dev_alloc(nv * 32)
-    ctx.upload(d_z0, z_pin[0])
+    d_z0 = ctx.dev_alloc(nv * 32) if args.full else None
+    if args.full:
+        ctx.upload(d_z0, z_pin[0])
     dev_steps = max(2, min(args.steps, 5))
-    if not multi:
+    if not args.full:
+        dev_ms = lat_ms = lat_page_ms = None
+    elif not multi:
         ctx.prove_witness_dev(key, dr, d_z0, r, s)
         ctx.sync()
         t1 = time.perf_counter()
@@ -1287,7 +1348,7 @@ def main():
     untiled = tiled = None
     if params_form and not multi and first_proof != want[0]:
         raise AssertionError('bench: the first proof after load_parameters differs from the pipelined proofs')
-    if params_form and not multi and not args.no_untiled and leg_fits('tiled', 10 * full_size):
+    if params_form and not multi and args.full and not args.no_untiled and leg_fits('tiled', 10 * full_size):
         t1 = time.perf_counter()
         dr_t = ctx.load_r1cs(r1cs, copies=copies)
         t_load = time.perf_counter() - t1
@@ -1380,7 +1441,8 @@ def main():
             raise AssertionError('bench: replica proof differs from the distributed proof')
         replica = world * (dev_steps + 1) / float(rep_t.item())
         leg_done('replicas')
-    ctx.dev_free(d_z0)
+    if args.full:
+        ctx.dev_free(d_z0)
 
     # ---- N > 1: the one-call form (one process drives all GPUs through fk_multi_prove_r1cs).  Every rank releases its GPU memory
     # first; the other ranks wait on a host-side (gloo) barrier so that nothing of theirs runs on the GPUs meanwhile.
@@ -1417,9 +1479,9 @@ def main():
         # dominant kernel: G1 bucket accumulation; achieved = algorithmic bytes / its HIP-event time
         achieved = (acc['units'] * G1_BYTES_PER_SCALAR_MUL) / acc_s / 1e9 if acc_s > 0 else 0.0
         traffic, traffic_src, traffic_err = pmc_traffic(args, log_m, n, world, acc, acc_s, achieved)
-        cal = ctx.calibrate()
+        cal = ctx.calibrate() if args.full else None           # (kernels of its own)
         modmul = acc['adds'] * MODMUL_PER_G1_MIXED_ADD
-        valu_peak = cal['mad_lane_ops_per_s'] / MUL_PIPE_OPS_PER_MODMUL
+        valu_peak = cal['mad_lane_ops_per_s'] / MUL_PIPE_OPS_PER_MODMUL if cal else None
         merged = bool(pre_levels.get('h'))
         kname = '%s<Fq> (G1 bucket accumulation)' % ('msm_accumulate_merged_kernel' if merged else 'msm_accumulate_kernel')
         fill = n / float(m)
@@ -1444,6 +1506,8 @@ def main():
             wl = ('%d rollup-style transactions (two depth-32 poseidon merkle proofs + one eddsa-poseidon signature each; a composition of the '
                   'reference\'s gadgets, tests/golden/rollup_tx_instance.npz) as ONE R1CS of %d rows = %.2f %% of the 2^%d domain (BASELINE configs[3] shape; '
                   'BASELINE.md config 4: rows = 2^25), %s' % (copies, n, 100.0 * fill, log_m,
+                  'the explicit system a `Parameters` gate blob decodes to (all %.3g matrix terms in HBM), loaded from the host\'s arrays through fk_r1cs_load_coded '
+                  '+ fk_key_load_bellman(checked); --full sets the prover up from the image itself' % float(sum(info['nnz'])) if lean_form else
                   'handed to the prover as a `Parameters` image (brotli gate blob + bellman key, mod.rs:150-175): fk_gates_decode -> fk_r1cs_load_gates '
                   '(all %.3g matrix terms explicit in HBM) + fk_key_load_bellman(checked)' % float(sum(info['nnz'])) if params_form else
                   'through fk_setup_tiled / fk_r1cs_load_tiled (one instance + a copy count)'))
@@ -1465,7 +1529,7 @@ def main():
             'data': 'synthetic',
             'config': {'workload': wl + '; per step: witness from pinned HOST memory (two-slot pipeline, two distinct witnesses alternating) -> device '
                                       'SpMV + quotient (6 NTTs) + G1 MSMs H/L/A/B1 + G2 MSM B2 + assembly; constraint system and valid key resident in HBM',
-                       'matrix_form': ('explicit, from a Parameters gate blob' if params_form else 'tiled (one instance + copy count)' if copies is not None else 'explicit'),
+                       'matrix_form': ('explicit, built on the host' if lean_form else 'explicit, from a Parameters gate blob' if params_form else 'tiled (one instance + copy count)' if copies is not None else 'explicit'),
                        'log2_domain': log_m, 'rows': n, 'domain_fill': fill, 'num_input': num_input, 'num_aux': num_aux,
                        'nnz': list(info['nnz']), 'witness_bytes_per_proof': nv * 32,
                        'distinct_transactions': (len(zs) if copies is not None else None),
@@ -1494,7 +1558,7 @@ def main():
             'roofline': rl_g1,
             'roofline_g2': rl_g2,
             'roofline_ntt': rl_ntt,
-            'roofline_valu': {
+            'roofline_valu': None if cal is None else {
                 'bound': 'valu-int-mul', 'kernel': kname,
                 'achieved': modmul / acc_s / 1e9 if acc_s > 0 else 0.0, 'peak': valu_peak / 1e9, 'unit': 'G modmul/s',
                 'frac': (modmul / acc_s) / valu_peak if acc_s > 0 else 0.0,
@@ -1519,6 +1583,9 @@ def main():
             },
             'prep_seconds': prep_s,
         }
+        if not args.full:
+            for k in ('device_resident_ms_per_step', 'latency_ms_per_proof', 'latency_pageable_ms_per_proof', 'latency_ms_per_proof_is', 'roofline_valu'):
+                del out[k]           # figures of runs of their own: --full
         if traffic_err:
             out['roofline']['traffic_error'] = traffic_err
         if replica_skipped is not None:
@@ -1530,7 +1597,7 @@ def main():
             out['preflight'] = preflight
         if multi_load is not None:
             out['load'] = multi_load
-        dg = check_digest(copies, two_witnesses, zs if copies is not None else None, want)
+        dg = check_digest(copies, two_witnesses, zs if copies is not None else None, want) if args.full else None
         if dg is not None:
             out['oracle_digest_check'] = dg
         import hashlib

@@ -74,3 +74,11 @@ def test_dump_outputs_writes_the_proof_bytes_exactly(tmp_path):
     got = np.load(out / 'proof.npy')
     assert got.dtype == np.float64 and got.shape == (256,)
     assert bytes(got.astype(np.uint8)) == proof and np.array_equal(got, np.arange(256, dtype=np.float64))
+
+
+def test_full_is_an_option():
+    """`--full` exists: everything beside the headline figure lives behind it"""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and '--full' in out.stdout and '--dump-outputs' in out.stdout

@@ -1,5 +1,5 @@
-"""bench.py end to end at a small size (subprocesses): the default single-GPU path with its cpu_baseline leg, and the
-multi-GPU code path rehearsed with ONE rank over real RCCL (FK_BENCH_REHEARSE=1: process group 'nccl', all_to_all_single /
+"""bench.py end to end at a small size (subprocesses): a plain run (the headline figure alone), and under --full the default single-GPU path
+with its cpu_baseline leg and the multi-GPU code path rehearsed with ONE rank over real RCCL (FK_BENCH_REHEARSE=1: process group 'nccl', all_to_all_single /
 all_gather on device tensors, distributed quotient and balanced schedule)."""
 import json
 import os
@@ -13,9 +13,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra_env, *args, gpus=1):
+def _run(extra_env, *args, gpus=1, full=True):
     env = dict(os.environ, **extra_env)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--steps', '2', '--warmup', '1', *args],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--steps', '2', '--warmup', '1', *(('--full',) if full else ()), *args],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -34,6 +34,30 @@ def _check_line(j):
     assert cb['single_thread']['cores'] == 1 and cb['single_thread']['value'] > 0
     assert j['device_resident_ms_per_step'] > 0
     assert j['config']['workload'] and 'model' not in j['config']
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """without --full a run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline fields as ever, none of the
+    optional legs or checks, no preflight child, no `Parameters` image -- and the SAME proof bytes as the --full run, whose prover is set up from the image"""
+    j = _run({}, '--copies', '6', '--dump-outputs', str(tmp_path / 'dump'), full=False)
+    assert j['unit'] == 'proofs/s' and j['higher_is_better'] is True and j['dtype'] == 'u32' and j['n_gpus'] == 1 and j['steps'] == 2 and j['warmup'] == 1
+    assert j['value'] > 0 and abs(j['value'] * j['ms_per_step'] - 1e3) < 1e-6 and '%d rows' % j['config']['rows'] in j['metric']
+    assert j['config']['matrix_form'] == 'explicit, built on the host' and j['config']['rows'] == 6 * 19270 + j['config']['num_input']
+    assert j['config']['distinct_witnesses_in_the_pipeline'] == 2 and set(j['config']['levels_plan']) == {'h', 'l', 'a', 'b_g1', 'b_g2'}
+    for k in ('cpu_baseline', 'proof_verified_by_pairing_check', 'oracle_digest_check', 'load', 'preflight', 'tiled', 'untiled', 'standalone', 'witness_sensitivity',
+              'secondary_1024_transactions', 'reference_published', 'device_resident_ms_per_step', 'latency_ms_per_proof', 'latency_pageable_ms_per_proof', 'roofline_valu'):
+        assert k not in j, k
+    assert set(j['legs']) == {'total_seconds', 'max_seconds', 'what'}, j['legs']
+    # what the timed steps launched is still accounted for (no run of its own)
+    assert j['roofline']['bound'] == 'hbm' and 0 < j['roofline']['frac'] < 1 and j['kernel_ms_per_step']['ntt_passes'] > 0
+    f = _run({}, '--copies', '6', '--no-cpu-baseline', '--no-other-sizes', '--no-standalone', '--no-untiled')
+    assert f['config']['matrix_form'] == 'explicit, from a Parameters gate blob' and f['config']['nnz'] == j['config']['nnz']
+    assert f['config']['msm_fixed_base_levels'] == j['config']['msm_fixed_base_levels'] and f['config']['msm_points'] == j['config']['msm_points']
+    assert len(j['proof_sha256']) == 2 and j['proof_sha256'] == f['proof_sha256']
+    import hashlib
+    dumped = np.load(tmp_path / 'dump' / 'proof.npy')
+    assert dumped.dtype == np.float64 and dumped.shape == (256,)
+    assert hashlib.sha256(bytes(dumped.astype(np.uint8))).hexdigest()[:16] == j['proof_sha256'][0]
 
 
 def test_bench_default_workload_small(tmp_path):
@@ -97,7 +121,7 @@ def _rank_run(n_ranks, copies, *extra, same_device=True):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'FK_DIST_QUOTIENT', 'FK_BENCH_SAME_DEVICE')}
     if same_device:
         env['FK_BENCH_SAME_DEVICE'] = '1'
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n_ranks), '--backend', 'gloo', '--steps', '2', '--warmup', '1',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n_ranks), '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full',
                           '--copies', str(copies), *extra], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1800)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     return json.loads(out.stdout.strip().splitlines()[-1])
@@ -189,7 +213,7 @@ def test_bench_plain_command_starts_its_own_ranks():
     (FK_BENCH_SAME_DEVICE=1, gloo).  The line also carries the one-call form of the same proof (fk_multi_prove_r1cs)."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['FK_BENCH_SAME_DEVICE'] = '1'
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--copies', '9'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full', '--copies', '9'],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     last = out.stdout.strip().splitlines()[-1]
@@ -204,7 +228,7 @@ def test_ranks_fall_back_to_their_own_key_shards_when_no_directory_can_hold_the_
     rank, and the ranks prove the tiled form from their own key shards as before round 6 -- the line says which form it measured and why"""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'FK_DIST_QUOTIENT')}
     env.update(FK_BENCH_SAME_DEVICE='1', FK_BENCH_IMAGE_DIR='none')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--copies', '9',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full', '--copies', '9',
                           '--no-replicas', '--no-single-process'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     j = json.loads(out.stdout.strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/ab_cu; mkdir -p $O; rm -f $O/*.log
 ARGS="--steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes --no-preflight --measure-traffic off"
-run() { local name=$1; shift; env "$@" python3 bench.py $ARGS > $O/$name.log 2>&1; echo "$name rc=$?"; }
+run() { local name=$1; shift; env "$@" python3 bench.py --full $ARGS > $O/$name.log 2>&1; echo "$name rc=$?"; }
 run k0 FK_LIB_VARIANT=exp FK_S1_THIN=0
 for k in 1 2; do for m in 0 1; do run k${k}_mode$m FK_LIB_VARIANT=exp FK_S1_THIN=0 FK_CU_SPLIT=$k FK_CU_SPLIT_MODE=$m; done; done
 run k0_again FK_LIB_VARIANT=exp FK_S1_THIN=0

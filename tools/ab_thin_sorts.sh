@@ -14,7 +14,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/ab_thin; mkdir -p $O; rm -f $O/*.log
 ARGS="--steps ${STEPS:-12} --warmup 4 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes --no-preflight --measure-traffic off"
 run() { # name, env...
   local name=$1; shift
-  env "$@" python3 bench.py $ARGS > $O/$name.log 2>&1; echo "$name rc=$?"
+  env "$@" python3 bench.py --full $ARGS > $O/$name.log 2>&1; echo "$name rc=$?"
 }
 for rep in 1 2; do
   run prod_$rep FK_DUMMY=1
@@ -38,7 +38,7 @@ for f in sorted(glob.glob('gpurun_out/ab_thin/*.log')):
 PY
 # one kernel trace of the most promising leg: where do the sort passes sit now?
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-FK_LIB_VARIANT=exp FK_S1_THIN=1 FK_PROVE_EARLY_SORTS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes --no-preflight --measure-traffic off > $O/kt.log 2>&1
+FK_LIB_VARIANT=exp FK_S1_THIN=1 FK_PROVE_EARLY_SORTS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes --no-preflight --measure-traffic off > $O/kt.log 2>&1
 python3 tools/trace_union.py $O/kt auto > $O/kt_union.txt 2>&1
 python3 tools/trace_window.py $O/kt ${WIN_K:-14} ${WIN_BEFORE:-160} 60 0.2 > $O/kt_boundary.txt 2>&1
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*.csv" -size +20M -delete

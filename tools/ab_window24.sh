@@ -6,7 +6,7 @@ out=gpurun_out/ab_window24.log
 : > $out
 run() {
   echo "== $*" >> $out
-  env FK_LIB_VARIANT=exp "$@" timeout 900 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-other-sizes --no-standalone --no-untiled 2>>$out.err | \
+  env FK_LIB_VARIANT=exp "$@" timeout 900 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-other-sizes --no-standalone --no-untiled 2>>$out.err | \
     python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({k: d.get(k) for k in ('value','ms_per_step','latency_ms_per_proof','device_resident_ms_per_step','proof_sha256','msm_fixed_base_levels')}))" >> $out
 }
 run FK_MSM_LB=11

@@ -12,8 +12,8 @@ for hostmask in 1 0; do
   FK_LIB_VARIANT=exp FK_CU_SPLIT=4 FK_CU_SPLIT_MODE=2 FK_CU_SPLIT_ALL=1 GUEST_SECONDS=150 python3 tools/cu_guest_probe.py > $O/guest_$hostmask.log 2>&1 &
   GP=$!
   for i in $(seq 1 120); do [ -f /tmp/fk_guest_ready ] && break; sleep 1; done
-  if [ $hostmask = 1 ]; then FK_LIB_VARIANT=exp FK_S1_THIN=0 FK_CU_SPLIT=4 FK_CU_SPLIT_MODE=2 python3 bench.py $HOSTARGS > $O/host_$hostmask.log 2>&1
-  else FK_LIB_VARIANT=exp FK_S1_THIN=0 python3 bench.py $HOSTARGS > $O/host_$hostmask.log 2>&1; fi
+  if [ $hostmask = 1 ]; then FK_LIB_VARIANT=exp FK_S1_THIN=0 FK_CU_SPLIT=4 FK_CU_SPLIT_MODE=2 python3 bench.py --full $HOSTARGS > $O/host_$hostmask.log 2>&1
+  else FK_LIB_VARIANT=exp FK_S1_THIN=0 python3 bench.py --full $HOSTARGS > $O/host_$hostmask.log 2>&1; fi
   echo "host rc=$?"
   kill $GP 2>/dev/null; wait $GP 2>/dev/null
   python3 - $O/host_$hostmask.log <<'PY'

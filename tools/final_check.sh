@@ -1,6 +1,6 @@
 #!/bin/bash
-# end-of-round check on the GPU box: the whole GPU suite, smoke(), the default bench command.  Output: gpurun_out/final/
-mkdir -p gpurun_out/final
-python3 -m pytest tests -m gpu -q --durations=8 > gpurun_out/final/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> gpurun_out/final/pytest_gpu.log; tail -3 gpurun_out/final/pytest_gpu.log
-python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/final/smoke.log 2>&1; tail -1 gpurun_out/final/smoke.log
-( time python3 bench.py ) > gpurun_out/final/bench.log 2> gpurun_out/final/bench.err; tail -c 600 gpurun_out/final/bench.log; grep real gpurun_out/final/bench.err
+# the whole GPU suite, smoke(), the whole benchmark (--full).  Output: ${OUT:-out}/final/
+O=${OUT:-out}/final; mkdir -p $O
+python3 -m pytest tests -m gpu -q --durations=8 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log; tail -3 $O/pytest_gpu.log
+python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
+( time python3 bench.py --full ) > $O/bench.log 2> $O/bench.err; tail -c 600 $O/bench.log; grep real $O/bench.err

@@ -8,8 +8,8 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/levels27; mkdir -p $O
 A="--workload synthetic --log2n 27 --steps 4 --warmup 2 --no-cpu-baseline --no-standalone --no-other-sizes --no-preflight --measure-traffic off"
-python3 bench.py $A > $O/planned.log 2>&1; echo "planned rc=$?"
-FK_MSM_PRECOMP=0 python3 bench.py $A > $O/nolevels.log 2>&1; echo "nolevels rc=$?"
+python3 bench.py --full $A > $O/planned.log 2>&1; echo "planned rc=$?"
+FK_MSM_PRECOMP=0 python3 bench.py --full $A > $O/nolevels.log 2>&1; echo "nolevels rc=$?"
 python3 - <<'PY'
 import json
 r={}

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/multi; mkdir -p $O
 run() { # name, nproc, env..., -- args
   name=$1; np=$2; shift 2
   env FK_BENCH_SAME_DEVICE=1 "$@" python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 --master-port 29577 \
-      bench.py --gpus $np --backend gloo --copies 64 --steps 2 --warmup 1 --no-cpu-baseline > $O/$name.log 2>&1
+      bench.py --full --gpus $np --backend gloo --copies 64 --steps 2 --warmup 1 --no-cpu-baseline > $O/$name.log 2>&1
   echo "$name rc=$?: $(grep '^{' $O/$name.log | python3 -c "
 import json,sys
 for l in sys.stdin:

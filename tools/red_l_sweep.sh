@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/red_l; mkdir -p $O; rm -f $O/*.log
 export FK_LIB_VARIANT=exp
 for rep in 1 2; do
   for L in 64 16 32 8; do
-    FK_MSM_RED_L_MERGED=$L python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes > $O/L${L}_$rep.log 2>&1
+    FK_MSM_RED_L_MERGED=$L python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes > $O/L${L}_$rep.log 2>&1
     python3 - "$O/L${L}_$rep.log" "L=$L rep=$rep" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -4,7 +4,7 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/rehearse; mkdir -p $O
 for n in ${RANKS:-2 4 8}; do
-  FK_BENCH_SAME_DEVICE=1 timeout 1500 python3 bench.py --gpus $n --backend gloo --steps 3 --warmup 1 --no-cpu-baseline --no-replicas > $O/n$n.log 2>&1
+  FK_BENCH_SAME_DEVICE=1 timeout 1500 python3 bench.py --full --gpus $n --backend gloo --steps 3 --warmup 1 --no-cpu-baseline --no-replicas > $O/n$n.log 2>&1
   echo "ranks=$n rc=$?"
   python3 - $O/n$n.log <<'PY'
 import json,sys

@@ -3,7 +3,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"; O=gpurun_out/serial; mkdir -p $O
 export FK_LIB_VARIANT=exp FK_MSM_PRE_DC=${PRE_DC:-3} FK_MSM_LANES=1 FK_PROVE_WITNESS_FIRST=0 FK_PROVE_SORTS_FIRST=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-untiled --no-standalone > $O/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-untiled --no-standalone > $O/kt.log 2>&1
 grep '^{' $O/kt.log | python3 -c "
 import json,sys
 for l in sys.stdin:

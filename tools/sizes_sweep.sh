@@ -1,15 +1,15 @@
 # ms per proof (pipelined loop, host witness) of the synthetic shape at several sizes + two rollup batch sizes: regression sweep
 set -u
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/sweep
+cd "$(dirname "$0")/.."; O=${OUT:-out}/sweep; mkdir -p $O
 for lg in ${SWEEP_LOGS:-20 22 24 26 27}; do
-  python3 bench.py --workload synthetic --log2n $lg --steps 8 --warmup 2 --no-cpu-baseline --no-standalone --no-other-sizes > gpurun_out/sweep/syn$lg.log 2>&1
+  python3 bench.py --full --workload synthetic --log2n $lg --steps 8 --warmup 2 --no-cpu-baseline --no-standalone --no-other-sizes > $O/syn$lg.log 2>&1
 done
 for c in 64 256; do
-  python3 bench.py --copies $c --steps 8 --warmup 2 --no-cpu-baseline --no-standalone --no-untiled --no-other-sizes > gpurun_out/sweep/roll$c.log 2>&1
+  python3 bench.py --full --copies $c --steps 8 --warmup 2 --no-cpu-baseline --no-standalone --no-untiled --no-other-sizes > $O/roll$c.log 2>&1
 done
-python3 - <<'PY'
-import json,glob
-for f in sorted(glob.glob('gpurun_out/sweep/*.log')):
+python3 - $O <<'PY'
+import json,glob,sys
+for f in sorted(glob.glob(sys.argv[1] + '/*.log')):
     ok=False
     for l in open(f):
         if l.startswith('{"metric"'):

@@ -7,7 +7,7 @@ export FK_LIB_VARIANT=exp
 run() {  # tag, env..., -- bench args
   tag=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" python3 bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes "$@" > $O/$tag.log 2>&1
+  env "${envs[@]}" python3 bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes "$@" > $O/$tag.log 2>&1
   python3 - "$O/$tag.log" "$tag" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -1,7 +1,7 @@
 # When does the HOST issue the launches of a proof's front, and when do they start on the GPU?  (GPU box; kernel + HIP API + copy traces, no counters)
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"; O=gpurun_out/trace_host; rm -rf $O; mkdir -p $O
-timeout 600 rocprofv3 --kernel-trace --hip-runtime-trace --memory-copy-trace --output-format csv -d $O/t -o t -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-untiled --no-standalone > $O/log 2>&1
+timeout 600 rocprofv3 --kernel-trace --hip-runtime-trace --memory-copy-trace --output-format csv -d $O/t -o t -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-untiled --no-standalone > $O/log 2>&1
 ls -la $O/t | head
 python3 - <<'PY'
 import csv, glob

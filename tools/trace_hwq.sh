@@ -2,9 +2,9 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"; O=gpurun_out/trace_hwq; rm -rf $O; mkdir -p $O
 F="--steps 6 --warmup 2 --no-cpu-baseline --no-untiled --no-standalone --no-other-sizes"
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/q4 -o k -- python3 bench.py $F > $O/q4.log 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/q4 -o k -- python3 bench.py --full $F > $O/q4.log 2>&1
 python3 tools/trace_window.py $O/q4 14 50 45 0.2 > $O/q4_boundary.txt 2>&1
-GPU_MAX_HW_QUEUES=8 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/q8 -o k -- python3 bench.py $F > $O/q8.log 2>&1
+GPU_MAX_HW_QUEUES=8 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/q8 -o k -- python3 bench.py --full $F > $O/q8.log 2>&1
 python3 tools/trace_window.py $O/q8 14 50 45 0.2 > $O/q8_boundary.txt 2>&1
 python3 - <<'PY'
 import csv, glob
