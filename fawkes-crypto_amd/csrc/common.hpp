@@ -46,8 +46,6 @@ struct MsmLane {
     bool ev_sorted_valid = false;
     DevBuf digits, sorted, totals, starts, perm, overlist, tasktab, partials, s2_cnt1, s2_seg, s2_cnt2, s2_tmp_idx, s2_tmp_lo, buckets;
     DevBuf buckets2;     // the buckets of a multiplication that reuses this lane's sort (B2 after B1): its accumulation is queued right behind B1's, before B1's tail has read `buckets`
-    void *h_stage = nullptr;        // pinned host staging: counters read back, oversized-bucket list, task tables
-    size_t h_cap = 0;
     const void *last_sort_scalars = nullptr; size_t last_sort_n = 0; unsigned last_sort_c = 0; bool last_merged = false;   // what `sorted` currently holds
     // ... the oversized-bucket state and tables that belong to it live on the device (msm.hip: MsmDyn, tasktab)
 };
@@ -210,7 +208,6 @@ namespace fk {
 
 std::string &tls_error();      // gatestream.hip: what fk_last_error(NULL) returns (context-free calls leave their message here)
 unsigned host_threads();       // gatestream.hip: FK_HOST_THREADS, else the cores this process may use
-bool cu_masks(::fk_ctx *ctx, std::vector<uint32_t> &compute, std::vector<uint32_t> &mem);      // msm.hip: FK_CU_SPLIT (experiment builds)
 
 // roctx ranges around the library's phases (tracing).  FK_ROCTX=1 binds libroctx64.so.4 with dlopen on first use; a trace taken with
 // `rocprofv3 --marker-trace --kernel-trace -- python3 bench.py ...` then shows which host call queued which kernels (the proof's kernels run

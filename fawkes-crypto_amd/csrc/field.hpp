@@ -203,7 +203,7 @@ struct alignas(16) Fp {
     // r1 = a0 b1 + a1 b0.  The sum of two products is below 2 q^2, its reduction below 1.26 q (lazy: q = 2p) or 1.38 q (q = p),
     // one conditional subtraction of q brings it back under q.
     static constexpr bool HAS_FQ2MUL =
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FK_FQ2_KARATSUBA)
+#if defined(__HIP_DEVICE_COMPILE__)
         INL;
 #else
         false;
@@ -222,7 +222,7 @@ struct alignas(16) Fp {
     // r1 = a^2, r2 = c^2.  Device, inlined flavour: the cross products a_i a_j (i < j) are taken once, against a doubled limb
     // (a < 2^255: the doubling loses no bit) -- 36 multiply-accumulates per square instead of 64 (tools/gen_mont_mul.py).
     static FK_HD void sqr2(const Fp &a, const Fp &c, Fp &r1, Fp &r2) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FK_NO_SQR2)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (INL) {
             Fp ad, ae, cd, ce;
 #pragma unroll
@@ -240,7 +240,7 @@ struct alignas(16) Fp {
     // a0 b0 + a1 b1 + a2 b2 + a3 b3, canonical operands.  Device, inlined flavour: one Montgomery reduction for the four products.
     static FK_HD Fp dot4(const Fp &a0, const Fp &b0, const Fp &a1, const Fp &b1, const Fp &a2, const Fp &b2, const Fp &a3, const Fp &b3) {
         static_assert(!P::LAZY, "dot4: the bound holds for canonical operands");
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FK_NO_DOT4)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (INL) return dot4_body_asm(a0, b0, a1, b1, a2, b2, a3, b3);
 #endif
         Fp x, y, u, v; mul2(a0, b0, a1, b1, x, y); mul2(a2, b2, a3, b3, u, v);
@@ -250,7 +250,7 @@ struct alignas(16) Fp {
     // a b - c d.  Device, inlined flavour: ONE Montgomery reduction for the sum a b + (q - c) d (mulsum_body_asm), i.e. a
     // reduction, a subtraction and their carry handling less than two products and a difference.
     static FK_HD Fp mulsub(const Fp &a, const Fp &b, const Fp &c, const Fp &d) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FK_NO_MULSUM)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (INL) return mulsum_body_asm(a, b, negq(c), d);
 #endif
         Fp x, y; mul2(a, b, c, d, x, y);
@@ -382,7 +382,7 @@ struct alignas(16) Fq2T {
         r1 = t;
     }
     static FK_HD Fq2 mulsub(const Fq2 &a, const Fq2 &b, const Fq2 &c, const Fq2 &d) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FK_NO_FQ2MULSUB)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (Fq::HAS_FQ2MUL) { Fq2 r; Fq::fq2mulsub(a.c0, a.c1, b.c0, b.c1, c.c0, c.c1, d.c0, d.c1, r.c0, r.c1); return r; }
 #endif
         return sub(mul(a, b), mul(c, d));

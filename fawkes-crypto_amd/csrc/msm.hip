@@ -299,7 +299,7 @@ __global__ __launch_bounds__(1024) void s2_tile_prefix_kernel(const uint32_t *se
 
 // First-pass scatter, LDS-staged like the second one: the chunk is walked in sub-tiles of S1_TILE entries; each sub-tile is
 // counted per high bin, laid out in bin order in LDS and written as contiguous runs (idx: 4 B, low bits: 2 B per entry) behind
-// the workgroup's per-bin cursors -- s2_scatter1n_body below (round 1's register-ranked form needed 128 registers and spilled).
+// the workgroup's per-bin cursors -- s2_scatter1_n1024_kernel below (round 1's register-ranked form needed 128 registers and spilled).
 // which segment does tile `t` belong to (tile_start is non-decreasing; empty segments own no tile)
 static __device__ __forceinline__ uint32_t s2_find_segment(const uint32_t *tile_start, uint32_t nseg, uint32_t t) {
     uint32_t lo = 0, hi = nseg;          // invariant: tile_start[lo] <= t < tile_start[hi]
@@ -459,35 +459,15 @@ __global__ __launch_bounds__(1024) void s2_scatter2_kernel(const uint32_t *tmp_i
 // First-pass scatter (two-atomic form): a lane owns S1_TILE / NT entries and keeps nothing about them between the phases -- the
 // counting phase only counts, the placing phase draws each entry's slot from a per-bin LDS cursor (round 1's register-ranked
 // form needed 128 registers and spilled).  256- and 512-lane shapes of both scatter kernels ("thin" workgroups that fit where one
-// accumulate workgroup has left) were built and measured in rounds 1 and 2: slower alone and no better underneath -- removed.
-template <uint32_t NT>
-static __device__ __forceinline__ uint32_t block_excl_scan_nt(uint32_t v, uint32_t *wsum, uint32_t *total) {
-    constexpr uint32_t NW = NT / 64;
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= (uint32_t)off) incl += t; }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < NW; w++) { const uint32_t x = wsum[w]; all += x; if (w < wv) base += x; }
-    __syncthreads();
-    *total = all;
-    return base + incl - v;
-}
-
-template <uint32_t NT>
-static __device__ __forceinline__ void s2_scatter1n_body(const uint32_t *digits, size_t n, size_t chunk, uint32_t nchunks, uint32_t LB,
-                                                           uint32_t nhi, const uint32_t *cnt1, const uint32_t *seg_start, uint32_t *tmp_idx,
-                                                           uint16_t *tmp_lo) {
+// accumulate workgroup has left) were built and measured in rounds 1, 2 and 6 (the last on a 32-register diet, to sit beside the
+// G2 accumulation): slower alone and no better underneath -- removed.
+__global__ __launch_bounds__(1024) void s2_scatter1_n1024_kernel(const uint32_t *digits, size_t n, size_t chunk, uint32_t nchunks, uint32_t LB,
+                                                                  uint32_t nhi, const uint32_t *cnt1, const uint32_t *seg_start, uint32_t *tmp_idx,
+                                                                  uint16_t *tmp_lo) {
+    constexpr uint32_t NT = 1024;                   // lanes per workgroup
     constexpr uint32_t BPL = S2_MAX_HI / NT;        // bins per lane
     constexpr uint32_t EPT = S1_TILE / NT;          // entries per lane and sub-tile
-#ifdef FK_S1_NO_PREFETCH
-    constexpr bool PREFETCH = false;
-#else
     constexpr bool PREFETCH = EPT <= 16;            // the sub-tile's digits live in registers and the NEXT sub-tile's are loaded while this one is written out
-#endif
     __shared__ uint32_t cursor[S2_MAX_HI];
     __shared__ uint32_t lcnt[S2_MAX_HI];
     __shared__ uint32_t lexc[S2_MAX_HI];        // exclusive offsets inside the sub-tile; advanced to the bins' ends by the placing phase
@@ -529,7 +509,7 @@ static __device__ __forceinline__ void s2_scatter1n_body(const uint32_t *digits,
 #pragma unroll
         for (uint32_t i = 0; i < BPL; i++) { c[i] = lcnt[tid * BPL + i]; mine += c[i]; }
         uint32_t total;
-        uint32_t ex = block_excl_scan_nt<NT>(mine, part, &total);
+        uint32_t ex = block_excl_scan_1024(mine, part, &total);
 #pragma unroll
         for (uint32_t i = 0; i < BPL; i++) { lexc[tid * BPL + i] = ex; ex += c[i]; }
         __syncthreads();
@@ -574,104 +554,6 @@ static __device__ __forceinline__ void s2_scatter1n_body(const uint32_t *digits,
         __syncthreads();
     }
 }
-
-// The same pass on a register diet (experiment builds, -DFK_S1_LEAN with -DFK_S1_NT=256): 32 VGPRs, so that one wave of it fits
-// into the 32 registers per SIMD lane that the G2 accumulation's two 240-register waves leave (profiles/r05_sort_kernel_resources.txt) and the pass
-// can run BESIDE that accumulation instead of waiting for drained compute units.  What the diet costs: no unrolling of the global loops (one load in
-// flight per lane, FK_S1_LEAN_VEC=4: one 16-byte load), 32-bit offsets inside the chunk, scheduling barriers that keep the compiler from software-
-// pipelining the write-out loop (which alone took the allocation from 32 to 46).  Same arguments, same result as s2_scatter1n_body.
-#ifdef FK_S1_LEAN
-#ifndef FK_S1_LEAN_TILE
-#define FK_S1_LEAN_TILE 4096
-#endif
-static constexpr uint32_t LEAN_TILE = FK_S1_LEAN_TILE;      // its own sub-tile: the production kernel of the same build keeps S1_TILE
-template <uint32_t NT>
-static __device__ __forceinline__ void s2_scatter1_lean_body(const uint32_t *digits, size_t n, size_t chunk, uint32_t nchunks, uint32_t LB,
-                                                              uint32_t nhi, const uint32_t *cnt1, const uint32_t *seg_start, uint32_t *tmp_idx,
-                                                              uint16_t *tmp_lo) {
-    constexpr uint32_t BPL = S2_MAX_HI / NT;
-    __shared__ uint32_t cursor[S2_MAX_HI];
-    __shared__ uint32_t lcnt[S2_MAX_HI];
-    __shared__ uint32_t lexc[S2_MAX_HI];
-    __shared__ uint32_t part[16];
-    __shared__ uint32_t stage_idx[LEAN_TILE];
-    __shared__ uint16_t stage_lo[LEAN_TILE];
-    __shared__ uint16_t stage_bin[LEAN_TILE];
-    __shared__ uint32_t stage_dig[LEAN_TILE];       // the sub-tile's digits: global memory is read once per entry
-    const uint32_t ch = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
-    const uint32_t *cnt = cnt1 + ((size_t)w * nchunks + ch) * nhi;
-    for (uint32_t b = tid; b < S2_MAX_HI; b += NT) cursor[b] = b < nhi ? seg_start[(size_t)w * nhi + b] + cnt[b] : 0;
-    const size_t c_lo = (size_t)ch * chunk, c_hi = c_lo + chunk < n ? c_lo + chunk : n;
-    const uint32_t lomask = (1u << LB) - 1;
-    uint32_t *oidx = tmp_idx + (size_t)w * n;
-    uint16_t *olo = tmp_lo + (size_t)w * n;
-    const uint32_t clen = (uint32_t)(c_hi > c_lo ? c_hi - c_lo : 0);
-    const uint32_t *dgc = digits + (size_t)w * n + c_lo;
-    const uint32_t base_idx = (uint32_t)c_lo;
-    for (uint32_t so = 0; so < clen; so += LEAN_TILE) {
-        const uint32_t cntt = clen - so < LEAN_TILE ? clen - so : LEAN_TILE;
-        const uint32_t *src = dgc + so;
-        const uint32_t sub = base_idx + so;
-        for (uint32_t b = tid; b < S2_MAX_HI; b += NT) lcnt[b] = 0;
-        __syncthreads();
-        // counting: the digits are parked in LDS (stage_idx) on the way, so global memory is read ONCE per entry
-#pragma clang loop unroll(disable)
-        for (uint32_t k = tid; k < cntt; k += NT) {
-            const uint32_t dd = src[k];
-            stage_dig[k] = dd;
-            const uint32_t bkt = dd & 0x7fffffffu;
-            if (bkt) atomicAdd(&lcnt[(bkt - 1) >> LB], 1u);
-        }
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-        uint32_t c[BPL], mine = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < BPL; i++) { c[i] = lcnt[tid * BPL + i]; mine += c[i]; }
-        uint32_t total;
-        uint32_t ex = block_excl_scan_nt<NT>(mine, part, &total);
-#pragma unroll
-        for (uint32_t i = 0; i < BPL; i++) { lexc[tid * BPL + i] = ex; ex += c[i]; }
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-        // placing: the digits come back out of LDS (stage_dig), each entry draws its slot from its bin's cursor
-#pragma clang loop unroll(disable)
-        for (uint32_t k = tid; k < cntt; k += NT) {
-            const uint32_t dd = stage_dig[k], bkt = dd & 0x7fffffffu;
-            if (bkt) {
-                const uint32_t bin = (bkt - 1) >> LB, q = atomicAdd(&lexc[bin], 1u);
-                stage_idx[q] = (sub + k) | (dd & 0x80000000u); stage_lo[q] = (uint16_t)((bkt - 1) & lomask); stage_bin[q] = (uint16_t)bin;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(disable)
-        for (uint32_t q = tid; q < total; q += NT) {
-            const uint32_t bn = stage_bin[q];
-            const uint32_t dst = cursor[bn] + (q - (lexc[bn] - lcnt[bn]));
-            oidx[dst] = stage_idx[q];
-            olo[dst] = stage_lo[q];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();
-        for (uint32_t b = tid; b < S2_MAX_HI; b += NT) cursor[b] += lcnt[b];
-        __syncthreads();
-    }
-}
-#endif
-
-#define S2N_ARGS1 const uint32_t *digits, size_t n, size_t chunk, uint32_t nchunks, uint32_t LB, uint32_t nhi, const uint32_t *cnt1, const uint32_t *seg_start, uint32_t *tmp_idx, uint16_t *tmp_lo
-#define S2N_PASS1 digits, n, chunk, nchunks, LB, nhi, cnt1, seg_start, tmp_idx, tmp_lo
-__global__ __launch_bounds__(1024) void s2_scatter1_n1024_kernel(S2N_ARGS1) { s2_scatter1n_body<1024>(S2N_PASS1); }
-// experiment builds only (-DFK_S1_NT=256 -DFK_S1_TILE=4096 [-DFK_S1_NO_PREFETCH]): the same pass in thin workgroups -- one wave per SIMD and few registers,
-// which could sit BESIDE the G2 accumulation's two 226-register waves per SIMD (rounds 1-2 measured thin shapes underneath G1 accumulations only)
-#ifdef FK_S1_NT
-#ifdef FK_S1_LEAN
-__global__ __launch_bounds__(FK_S1_NT) void s2_scatter1_thin_kernel(S2N_ARGS1) { s2_scatter1_lean_body<FK_S1_NT>(S2N_PASS1); }
-#else
-__global__ __launch_bounds__(FK_S1_NT) void s2_scatter1_thin_kernel(S2N_ARGS1) { s2_scatter1n_body<FK_S1_NT>(S2N_PASS1); }
-#endif
-#endif
 
 // ------------------------------------------------------------------------------------------ bucket -> lane assignment
 // A wave runs as long as its longest bucket, so lanes are handed buckets of (nearly) equal length: buckets are
@@ -782,15 +664,11 @@ static __device__ __forceinline__ void block_reduce_256(Xyzz<F> &acc, Xyzz<F> *s
 // The per-lane walk of a bucket: the 8 x 32-bit XYZZ accumulator of curve.hpp.  (A 9 x 29-bit-limb accumulator -- no carry-out
 // per multiply-accumulate, no conditional subtractions -- was built in round 2, bit-exact and NOT faster in place: 234 against
 // 216 ms per proof; DESIGN.md section 3.3.  Removed in round 3.)
-#if defined(__HIP_DEVICE_COMPILE__)
-template <class F, int MODE> struct Walker {       // MODE 0
-    Xyzz<F> acc = Xyzz<F>::inf();
-    __device__ __forceinline__ void add(const Affine<F> &p, bool neg) { acc.add_mixed(affine_neg_if(p, neg)); }
-    __device__ __forceinline__ Xyzz<F> result() const { return acc; }
-};
-// MODE 2: the accumulator's coordinates live in [0, 2p) (field.hpp, LAZY): no conditional subtraction behind any of the ten
+// The accumulator's coordinates live in [0, 2p) (field.hpp, LAZY): no conditional subtraction behind any of the ten
 // products of a mixed addition; the bucket is made canonical when it is stored.  A loaded point is canonical, hence valid.
-template <class F> struct Walker<F, 2> {
+// (The canonical walker -- reduced after every product -- lost in round 2, 195.7 against 191.1 ms per proof, and is gone.)
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class F> struct Walker {
     using FL = typename LazyOf<F>::type;
     Xyzz<FL> acc = Xyzz<FL>::inf();
     __device__ __forceinline__ void add(const Affine<F> &p, bool neg) {
@@ -807,7 +685,7 @@ template <class F> struct Walker<F, 2> {
     }
 };
 #else
-template <class F, int MODE> struct Walker {       // host pass: declarations only
+template <class F> struct Walker {       // host pass: declarations only
     void add(const Affine<F> &, bool) {}
     Xyzz<F> result() const { return Xyzz<F>::inf(); }
 };
@@ -816,7 +694,7 @@ template <class F, int MODE> struct Walker {       // host pass: declarations on
 // G2: 2.  With the compiler's own add/sub code the inlined Fq2 mixed addition wanted 256 VGPRs + ~180 AGPRs and forcing 2
 // waves spilled ~260 registers (41 ms vs 33 ms at 2^25); since the generated carry-chain add/sub (addsub_gfx950.inc) it
 // needs 226 VGPRs and runs at 2 waves per SIMD without spills: 23.4 -> 13.7 ms.
-template <class F, int MINW, int MODE>
+template <class F, int MINW>
 __global__ __launch_bounds__(256, MINW) void msm_accumulate_kernel(const Affine<F> *bases, const uint32_t *sorted, size_t n,
                                                              const uint32_t *starts, const uint32_t *totals, uint32_t B,
                                                              uint32_t W, const MsmDyn *dyn, const uint32_t *perm, Xyzz<F> *buckets) {
@@ -828,7 +706,7 @@ __global__ __launch_bounds__(256, MINW) void msm_accumulate_kernel(const Affine<
     const uint32_t *src = sorted + (size_t)w * n + starts[g];
     uint32_t cnt = totals[g];
     if (cnt > cap) cnt = cap;
-    Walker<F, MODE> acc;
+    Walker<F> acc;
     for (uint32_t k = 0; k < cnt; k++) {
         const uint32_t e = src[k];
         Affine<F> p = bases[e & 0x7fffffffu];
@@ -842,7 +720,7 @@ __global__ __launch_bounds__(256, MINW) void msm_accumulate_kernel(const Affine<
 // The walk is ONE loop over the bucket's merged length mt[b] with a (window, position) cursor: the lanes of a wave are
 // size-ordered by that merged length, so they stay in step; a loop per window would run every window to the longest of the 64
 // per-window counts (Poisson: 1.6 x the mean at a load of 16).
-template <class F, int MINW, int MODE>
+template <class F, int MINW>
 __global__ __launch_bounds__(256, MINW) void msm_accumulate_merged_kernel(const Affine<F> *bases, const Affine<F> *lev, const uint32_t *sorted, size_t n,
                                                                     const uint32_t *starts, const uint32_t *totals, uint32_t B,
                                                                     uint32_t W, const MsmDyn *dyn, const uint32_t *perm, const uint32_t *mt, Xyzz<F> *buckets) {
@@ -851,7 +729,7 @@ __global__ __launch_bounds__(256, MINW) void msm_accumulate_merged_kernel(const 
     const uint32_t cap = dyn->cap;
     const uint32_t b = perm[t];
     const uint32_t total = mt[b];
-    Walker<F, MODE> acc;
+    Walker<F> acc;
     uint32_t w = 0, k = 0, cnt = 0;
     const uint32_t *src = nullptr;
     const Affine<F> *bw = bases;
@@ -931,7 +809,7 @@ struct OverBucket { uint32_t g, task0, ntask; };
 // several waves per SIMD in flight (the multiply is a serial chain, one wave alone cannot fill the VALU).
 // The per-lane walk uses the inlined multiply (F); the wave64 shuffle reduction runs on the
 // layout-identical cold twin (FC).
-template <class F, class FC, int MODE>
+template <class F, class FC>
 __global__ __launch_bounds__(64) void msm_overflow_kernel(const Affine<F> *bases0, const Affine<F> *lev, const uint32_t *sorted, size_t n,
                                                           const uint32_t *starts, const uint32_t *totals, uint32_t B,
                                                           const MsmDyn *dyn, const Task *tasks, Xyzz<FC> *partials) {
@@ -944,7 +822,7 @@ __global__ __launch_bounds__(64) void msm_overflow_kernel(const Affine<F> *bases
         const uint32_t size = totals[t.g];
         const uint32_t lo = cap + t.seg * SEG;
         const uint32_t hi = lo + SEG < size ? lo + SEG : size;
-        Walker<F, MODE> wk;
+        Walker<F> wk;
         for (uint32_t k = lo + threadIdx.x; k < hi; k += 64) {
             const uint32_t e = src[k];
             wk.add(bases[e & 0x7fffffffu], (e >> 31) != 0);
@@ -1099,36 +977,15 @@ __global__ __launch_bounds__(256) void msm_fold_partials_kernel(const Xyzz<F> *w
         }                                                                                         \
     } while (0)
 
-// every stream of a context, created together and in one order (called by fk_init).  HIP maps streams onto a handful of hardware queues
+// every stream of a context, created together and in one order (called by fk_init, and by fk_trim after it has released them: lanes that have
+// a stream are skipped).  HIP maps streams onto a handful of hardware queues
 // in creation order, and streams that share a queue serialise: with lazily created streams the mapping depended on which call a
 // process happened to make first -- a process that proved once through fk_prove_r1cs before it pipelined got its copy stream onto the
 // hardware queue of the B pair's lane, the upload's completion then sat behind the G2 tail, and the early front of every pipelined
 // proof started ~12 ms late (251 against 228 ms per proof on one box; profiles/r05_stream_order_ab.log).  The order here is the one
 // the benchmark process of rounds 2-4 happened to create: main (fk_init), copy, auxiliary, the four lanes.
-// FK_CU_SPLIT=k (experiment builds; 1 <= k <= 4): k of every 8 compute units are set aside -- the lane streams (sorts, accumulations, tails) are created
-// with a CU mask that leaves them out.  Step 1 of "memory-bound work on compute units of its own": what does an accumulation lose when it may
-// use only (8 - k) / 8 of the chip?  FK_CU_SPLIT_MODE picks which units of the mask are set aside: 0 = bits with i mod 8 < k, 1 = bits with (i div 8) mod 8 < k
-// (how mask bits map to XCDs is not documented for gfx950: with a round-robin mapping mode 0 sets whole XCDs aside and mode 1 units of every XCD, with a
-// linear mapping the other way round).
-bool cu_masks(fk_ctx *ctx, std::vector<uint32_t> &compute, std::vector<uint32_t> &mem) {
-    const int k = tune("FK_CU_SPLIT", 0), mode = tune("FK_CU_SPLIT_MODE", 0);
-    if (k < 1 || k > 4) return false;
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, ctx->device) != hipSuccess) return false;
-    const int ncu = pr.multiProcessorCount, words = (ncu + 31) / 32;
-    compute.assign(words, 0); mem.assign(words, 0);
-    for (int i = 0; i < ncu; i++) {
-        // measured (tools/mulbench/cumask.hip, profiles/r06_cu_mask_semantics.log): mask bit i = XCD i mod 8, unit i div 8 of that XCD; an XCD whose bits are
-        // ALL clear is not switched off, it runs unrestricted -- so mode 0 is a no-op; mode 2 sets aside the units j < k of EVERY XCD (j = i div 8)
-        const bool m = mode == 0 ? (i % 8) < k : mode == 1 ? ((i / 8) % 8) < k : (i / 8) < k;
-        (m ? mem : compute)[i / 32] |= 1u << (i % 32);
-    }
-    return true;
-}
-
+// (Lane streams restricted to a part of the chip by a CU mask were tried in round 6 and did not pay: DESIGN.md section 7 [1g].)
 int streams_init(fk_ctx *ctx) {
-    std::vector<uint32_t> m_compute, m_mem;
-    const bool split = cu_masks(ctx, m_compute, m_mem);
     if (!ctx->copy_st) FK_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_st, hipStreamNonBlocking));
     if (!ctx->aux) {
         FK_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
@@ -1136,28 +993,229 @@ int streams_init(fk_ctx *ctx) {
     }
     for (MsmLane &ln : ctx->lanes) {
         if (ln.st) continue;
-        if (split) FK_HIP(ctx, hipExtStreamCreateWithCUMask(&ln.st, (uint32_t)m_compute.size(), ((tune("FK_CU_SPLIT_INVERT", 0) || tune("FK_CU_SPLIT_ALL", 0)) ? m_mem : m_compute).data()));      // (INVERT: sanity check of the mask; ALL: a guest context, everything on the set-aside units)
-        else FK_HIP(ctx, hipStreamCreateWithFlags(&ln.st, hipStreamNonBlocking));
+        FK_HIP(ctx, hipStreamCreateWithFlags(&ln.st, hipStreamNonBlocking));
         FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_in, hipEventDisableTiming));
         FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_sorted, hipEventDisableTiming));
     }
-    if (split && getenv("FK_DEBUG")) fprintf(stderr, "[fk] FK_CU_SPLIT: lane streams masked to %zu words (compute %08x.., set aside %08x..)\n", m_compute.size(), m_compute[0], m_mem[0]);
     return FK_OK;
 }
 
-static int lane_init(fk_ctx *ctx, MsmLane &ln) {
-    if (ln.st) return FK_OK;
-    FK_HIP(ctx, hipStreamCreateWithFlags(&ln.st, hipStreamNonBlocking));
-    FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_in, hipEventDisableTiming));
-    FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_sorted, hipEventDisableTiming));
+// pinned host staging with room for bytes + pad, grow-only (a quarter of slack); callers own the ordering
+static int pinned_reserve(fk_ctx *ctx, void **p, size_t *cap, size_t bytes, size_t pad) {
+    if (bytes + pad <= *cap) return FK_OK;
+    if (*p) { FK_HIP(ctx, hipHostFree(*p)); *p = nullptr; *cap = 0; }
+    FK_HIP(ctx, hipHostMalloc(p, bytes + (bytes >> 2) + pad, hipHostMallocDefault));
+    *cap = bytes + (bytes >> 2) + pad;
     return FK_OK;
 }
 
-static int lane_stage(fk_ctx *ctx, MsmLane &ln, size_t bytes) {     // pinned staging, grow-only; callers own the ordering
-    if (bytes <= ln.h_cap) return FK_OK;
-    if (ln.h_stage) { FK_HIP(ctx, hipHostFree(ln.h_stage)); ln.h_stage = nullptr; ln.h_cap = 0; }
-    FK_HIP(ctx, hipHostMalloc(&ln.h_stage, bytes + (bytes >> 2) + 4096, hipHostMallocDefault));
-    ln.h_cap = bytes + (bytes >> 2) + 4096;
+// What the stages of one multiplication share: msm_begin fills it in, msm_reserve binds the pointers into the lane's scratch, the
+// deferred pieces (ctx->defer_back) keep a copy.
+template <class F>
+struct MsmJob {
+    fk_ctx *ctx;
+    MsmPlan p;
+    MsmLane *ln;
+    MsmTail *tl;
+    const Affine<F> *bases, *lev;       // lev: the precomputed levels of the merged form, else null
+    const Fr *scalars;
+    size_t n, WB, max_tasks, max_tiles, wp_bytes;
+    uint32_t WR;                        // bucket sets to reduce
+    bool merged, have_sort;             // have_sort: the lane's previous sort is reused (B2 after B1)
+    MsmDyn *dyn;                        // device-side state of this lane's sort
+    uint32_t *digits, *sorted, *totals, *starts, *perm;
+    Task *tasks;
+    OverBucket *obs;
+    Xyzz<F> *winparts;                  // (the bucket buffer is bound in the back half: bucket_buf)
+};
+
+// Sizes the lane's scratch and the tail's buffers for this plan, grows what is too small and binds the job's pointers.
+template <class F>
+static int msm_reserve(MsmJob<F> &j) {
+    fk_ctx *ctx = j.ctx;
+    const MsmPlan &p = j.p;
+    MsmLane &ln = *j.ln;
+    MsmTail &tl = *j.tl;
+    const size_t n = j.n, WB = j.WB = (size_t)p.W * p.B;
+    j.WR = j.merged ? 1 : p.W;
+    // bucket reduction: the flat form (up to 64 buckets per lane, then a double-and-add by the lane's offset).  A hierarchical form
+    // (8 buckets per lane, wave-level suffix sums) was built in round 2: a 2.5x shorter serial chain, 1.6x the additions, slower
+    // everywhere (171.5 -> 178.3 ms per proof at 2^25) -- removed in round 3.
+    j.wp_bytes = (size_t)j.WR * sizeof(Xyzz<F>);                                   // ONE point per bucket set (folded on the device)
+    const size_t wp_dev_bytes = (size_t)j.WR * (p.nblk + 1) * sizeof(Xyzz<F>);    // ... behind the nblk partial sums of every set
+    // oversized buckets: at most OVER_MAX are tabled; their segment tasks are bounded by max(2048, W n / SEG_MAX) + one per bucket
+    const size_t max_tasks = j.max_tasks = std::max<size_t>(2048, (size_t)p.W * n / SEG_MAX) + OVER_MAX + 64;
+    const uint32_t nseg = p.W * p.nhi;
+    const size_t max_tiles = j.max_tiles = (size_t)p.W * ((n + S2_TILE - 1) / S2_TILE) + nseg + 1;
+    // Growing a buffer frees the old one: everything queued on this lane must be finished first.
+    struct Need { DevBuf *b; size_t bytes; };
+    const Need needs[] = {
+        {&ln.digits, (size_t)p.W * n * 4}, {&ln.sorted, (size_t)p.W * n * 4}, {&ln.totals, WB * 4}, {&ln.starts, WB * 4},
+        {&ln.perm, WB * 4 + SIZE_BINS * 4}, {&ln.overlist, OVER_MAX * sizeof(OverEntry) + sizeof(MsmDyn) + 64}, {j.have_sort ? &ln.buckets2 : &ln.buckets, WB * sizeof(Xyzz<F>)},
+        {&ln.tasktab, max_tasks * sizeof(Task) + OVER_MAX * sizeof(OverBucket) + 64}, {&ln.partials, max_tasks * sizeof(Xyzz<F>)},
+        {&ln.s2_cnt1, (size_t)p.W * p.nchunks * p.nhi * 4}, {&ln.s2_seg, ((size_t)nseg * 4 + 2) * 4}, {&ln.s2_cnt2, max_tiles * p.nlo * 4},
+        {&ln.s2_tmp_idx, (size_t)p.W * n * 4}, {&ln.s2_tmp_lo, (size_t)p.W * n * 2}};
+    bool grow = false;
+    for (const Need &nd : needs) grow = grow || nd.bytes > nd.b->cap;
+    if (grow) {
+        FK_HIP(ctx, hipStreamSynchronize(ln.st));
+        for (const Need &nd : needs) FK_HIP(ctx, nd.b->reserve(nd.bytes));
+        if (!j.have_sort) ln.last_sort_scalars = nullptr;
+    }
+    FK_HIP(ctx, tl.d_wp.reserve(wp_dev_bytes));
+    FK_TRY(pinned_reserve(ctx, &tl.h_wp, &tl.h_cap, j.wp_bytes, 16));         // + the additions counter and the error word
+    j.dyn = (MsmDyn *)((char *)ln.overlist.p + OVER_MAX * sizeof(OverEntry));
+    j.tasks = ln.tasktab.as<Task>();
+    j.obs = (OverBucket *)((char *)ln.tasktab.p + ((max_tasks * sizeof(Task) + 15) & ~(size_t)15));
+    j.digits = ln.digits.as<uint32_t>(); j.sorted = ln.sorted.as<uint32_t>();
+    j.totals = ln.totals.as<uint32_t>(); j.starts = ln.starts.as<uint32_t>();
+    j.winparts = tl.d_wp.as<Xyzz<F>>();
+    j.perm = ln.perm.as<uint32_t>();
+    return FK_OK;
+}
+
+// second-pass scatter: the instantiation whose LDS tables hold the plan's low bins
+static void launch_scatter2(const MsmPlan &p, uint32_t n_tiles, hipStream_t st, const uint32_t *tmp_idx, const uint16_t *tmp_lo, size_t n, const uint32_t *tile_start, uint32_t nseg,
+                            const uint32_t *seg_start, const uint32_t *seg_size, const uint32_t *cnt2, const uint32_t *starts, uint32_t *sorted) {
+    const auto kernel = p.nlo <= 1024 ? s2_scatter2_kernel<1024> : (p.nlo <= 2048 ? s2_scatter2_kernel<2048> : s2_scatter2_kernel<4096>);
+    hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(1024), 0, st, tmp_idx, tmp_lo, n, p.nhi, p.nlo, p.B, tile_start, nseg, seg_start, seg_size, cnt2, starts, sorted);
+}
+
+// digits and the two-pass bucket sort; the lane remembers what its `sorted` holds (B2 reuses B1's)
+template <class F>
+static int queue_sort(const MsmJob<F> &j) {
+    fk_ctx *ctx = j.ctx;
+    const MsmPlan &p = j.p;
+    MsmLane &ln = *j.ln;
+    hipStream_t st = ln.st;
+    const size_t n = j.n;
+    const uint32_t nseg = p.W * p.nhi;
+    ln.last_sort_scalars = nullptr;
+    hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)(((n + 1) / 2 + 63) / 64)), dim3(64), 0, st, j.scalars, n, p.cb, p.wide, p.W, j.digits);
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_digits");
+    FK_HIP(ctx, hipMemsetAsync(j.dyn, 0, sizeof(MsmDyn), st));
+    uint32_t *cnt1 = ln.s2_cnt1.as<uint32_t>();
+    uint32_t *seg_size = ln.s2_seg.as<uint32_t>(), *seg_start = seg_size + nseg, *seg_tiles = seg_start + nseg, *tile_start = seg_tiles + nseg;
+    uint32_t *cnt2 = ln.s2_cnt2.as<uint32_t>(), *tmp_idx = ln.s2_tmp_idx.as<uint32_t>();
+    uint16_t *tmp_lo = ln.s2_tmp_lo.as<uint16_t>();
+    hipLaunchKernelGGL(s2_hist1_kernel, dim3(p.nchunks, p.W), dim3(SORT_THREADS), p.nhi * 4, st, j.digits, n, p.chunk, p.nchunks, p.LB, p.nhi, cnt1);
+    hipLaunchKernelGGL(s2_prefix1_kernel, dim3(p.W), dim3(1024), p.nhi * 4, st, cnt1, p.nchunks, p.nhi, seg_size, seg_start, seg_tiles);
+    hipLaunchKernelGGL(s2_tile_prefix_kernel, dim3(1), dim3(1024), 0, st, seg_tiles, nseg, tile_start);
+    hipLaunchKernelGGL(s2_scatter1_n1024_kernel, dim3(p.nchunks, p.W), dim3(1024), 0, st, j.digits, n, p.chunk, p.nchunks, p.LB, p.nhi, cnt1, seg_start, tmp_idx, tmp_lo);
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_sort_pass1");
+    // The second pass is launched over the host's BOUND on the tile count (every segment's last tile may be partial:
+    // W * ceil(n / tile) + #segments); workgroups beyond the actual count leave at once.  Reading the count back cost a
+    // host round trip in the middle of every sort.
+    const uint32_t n_tiles = (uint32_t)j.max_tiles;
+    hipLaunchKernelGGL(s2_hist2_kernel, dim3(n_tiles), dim3(256), p.nlo * 4, st, tmp_lo, n, p.nhi, p.nlo, tile_start, nseg, seg_start, seg_size, cnt2);
+    hipLaunchKernelGGL(s2_prefix2_kernel, dim3((nseg + 3) / 4), dim3(256), 0, st, cnt2, nseg, p.nhi, p.nlo, p.B, tile_start, seg_start, p.cap ? p.cap : 1u, j.totals, j.starts, j.dyn);
+    launch_scatter2(p, n_tiles, st, tmp_idx, tmp_lo, n, tile_start, nseg, seg_start, seg_size, cnt2, j.starts, j.sorted);
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_sort_pass2");
+    ln.last_sort_scalars = (const void *)j.scalars; ln.last_sort_n = n; ln.last_sort_c = p.c; ln.last_merged = j.merged;
+    return FK_OK;
+}
+
+// oversized buckets (skewed scalars), size ordering: all on the device (MsmDyn) -- nothing here waits for the host
+template <class F>
+static int queue_size_order(const MsmJob<F> &j) {
+    fk_ctx *ctx = j.ctx;
+    const MsmPlan &p = j.p;
+    MsmLane &ln = *j.ln;
+    hipStream_t st = ln.st;
+    const size_t WB = j.WB;
+    MsmDyn *dyn = j.dyn;
+    uint32_t *totals = j.totals, *perm = j.perm, *size_bins = perm + WB;
+    unsigned long long *d_adds = &dyn->adds;
+    static const int t_many = tune("FK_MSM_OVER_MANY", 2048);
+    // "few": every oversized bucket costs a wave per segment plus a 256-lane fold workgroup -- with 4e5 of them, what round 1's
+    // WB / 64 allowed at 2^25, the overflow + fold kernels took 70 ms of a proof whose witness held each value 341 times
+    const uint32_t many = (uint32_t)std::min<size_t>(std::max<size_t>((size_t)t_many, WB / 8192), OVER_MAX - 64);
+    hipLaunchKernelGGL(msm_cap_kernel, dim3(1), dim3(64), 0, st, dyn, p.cap ? p.cap : 1u, many);
+    hipLaunchKernelGGL(msm_over_list_kernel, dim3((unsigned)((WB + 255) / 256)), dim3(256), 0, st, totals, WB, ln.overlist.as<OverEntry>(), dyn);
+    hipLaunchKernelGGL(msm_tasks_kernel, dim3(1), dim3(1024), 0, st, ln.overlist.as<OverEntry>(), dyn, p.B, j.merged ? 1 : 0, j.tasks, (uint32_t)j.max_tasks, j.obs);
+    // size-ordered bucket -> lane assignment
+    FK_HIP(ctx, hipMemsetAsync(size_bins, 0, SIZE_BINS * 4, st));
+    if (j.merged) {     // one bucket set: order its B buckets by their length over all windows (perm[0, B); lengths kept behind it)
+        uint32_t *mt = perm + p.B;
+        hipLaunchKernelGGL(msm_merge_totals_kernel, dim3(std::min<uint32_t>((p.B + 255) / 256, 1024)), dim3(256), 0, st, totals, p.B, p.W, dyn, mt, d_adds);
+        hipLaunchKernelGGL(msm_size_hist_kernel, dim3((unsigned)std::min<size_t>((p.B + 255) / 256, 1024)), dim3(256), 0, st, mt, (size_t)p.B, dyn, p.W, size_bins, (unsigned long long *)nullptr);
+        hipLaunchKernelGGL(msm_size_scan_kernel, dim3(1), dim3(SIZE_BINS), 0, st, size_bins);
+        hipLaunchKernelGGL(msm_size_scatter_kernel, dim3((unsigned)((p.B + 1023) / 1024)), dim3(1024), 0, st, mt, (size_t)p.B, dyn, p.W, size_bins, perm);
+    } else {
+        hipLaunchKernelGGL(msm_size_hist_kernel, dim3((unsigned)std::min<size_t>((WB + 255) / 256, 1024)), dim3(256), 0, st, totals, WB, dyn, 1u, size_bins, d_adds);
+        hipLaunchKernelGGL(msm_size_scan_kernel, dim3(1), dim3(SIZE_BINS), 0, st, size_bins);
+        hipLaunchKernelGGL(msm_size_scatter_kernel, dim3((unsigned)((WB + 1023) / 1024)), dim3(1024), 0, st, totals, WB, dyn, 1u, size_bins, perm);
+    }
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_size_order");
+    if (ctx->debug) {
+        MsmDyn h{};
+        FK_HIP(ctx, hipMemcpy(&h, dyn, sizeof h, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[fk] msm n=%zu c=%u (W=%u: %u x %u bits + %u x %u bits) cap=%u (plan %u): %u oversized buckets, %u tasks of %u entries, %u fold groups\n", j.n, p.c,
+                p.W, p.wide, p.cb + 1, p.W - p.wide, p.cb, h.cap, p.cap, h.n_over, h.n_tasks, h.seg, h.n_obs);
+        fflush(stderr);
+    }
+    return FK_OK;
+}
+
+// bound late (inside the pieces): a multiplication begun on this lane in between may have GROWN a buffer, i.e. moved it
+template <class F>
+static Xyzz<F> *bucket_buf(const MsmJob<F> &j) { return (j.have_sort ? j.ln->buckets2 : j.ln->buckets).template as<Xyzz<F>>(); }
+
+// The back of a multiplication, first piece: the bucket accumulation.  MINW: msm_accumulate_kernel.
+template <class F>
+static int queue_accumulate(MsmJob<F> j) {
+    fk_ctx *ctx = j.ctx;
+    const MsmPlan &p = j.p;
+    hipStream_t st = j.ln->st;
+    constexpr int MINW = std::is_same<F, Fq>::value ? 4 : 2;
+    Xyzz<F> *buckets = bucket_buf(j);
+    std::vector<EventPair> &evv = (sizeof(F) == sizeof(Fq)) ? ctx->ev_acc : ctx->ev_acc2;
+    FK_TRY(stats_begin(ctx, evv, (uint64_t)j.n, st));
+    if (j.merged)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_merged_kernel<F, MINW>), dim3((p.B + 255) / 256), dim3(256), 0, st, j.bases, j.lev, j.sorted, j.n,
+                           j.starts, j.totals, p.B, p.W, j.dyn, j.perm, j.perm + p.B, buckets);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_kernel<F, MINW>), dim3((unsigned)((j.WB + 255) / 256)), dim3(256), 0, st, j.bases, j.sorted, j.n,
+                           j.starts, j.totals, p.B, p.W, j.dyn, j.perm, buckets);
+    FK_HIP(ctx, hipGetLastError());
+    FK_TRY(stats_end(ctx, evv, st));
+    if (!ctx->ev_acc_done) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_acc_done, hipEventDisableTiming));
+    FK_HIP(ctx, hipEventRecord(ctx->ev_acc_done, st)); ctx->ev_acc_done_valid = true;
+    FK_DBG_ST(ctx, st, "msm_accumulate");
+    return FK_OK;
+}
+
+// ... second piece, the tail: oversized buckets, bucket reduction, download of the window sums
+template <class F>
+static int queue_tail(MsmJob<F> j) {
+    using FC = typename ColdOf<F>::type;   // layout-identical field with an out-of-line multiply
+    fk_ctx *ctx = j.ctx;
+    const MsmPlan &p = j.p;
+    MsmLane &ln = *j.ln;
+    MsmTail &tl = *j.tl;
+    hipStream_t st = ln.st;
+    Xyzz<F> *buckets = bucket_buf(j);
+    // oversized buckets: fixed grids looping over the device-built tables (they leave at once when there is nothing to do)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_kernel<F, FC>), dim3(2048), dim3(64), 0, st,
+                       j.bases, j.lev, j.sorted, j.n, j.starts, j.totals, p.B, j.dyn, j.tasks, ln.partials.as<Xyzz<FC>>());
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_overflow");
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_fold_kernel<F>), dim3(256), dim3(256), 0, st, j.obs, j.dyn, ln.partials.as<Xyzz<F>>(), buckets);
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_overflow_fold");
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_bucket_reduce_kernel<F>), dim3(p.nblk, j.WR), dim3(256), 0, st, buckets, p.B, p.L, p.T, p.nblk, j.winparts);
+    Xyzz<F> *folded = j.winparts + (size_t)j.WR * p.nblk;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_fold_partials_kernel<F>), dim3(j.WR), dim3(256), 0, st, j.winparts, p.nblk, folded);
+    FK_HIP(ctx, hipGetLastError());
+    FK_HIP(ctx, hipMemcpyAsync(tl.h_wp, folded, j.wp_bytes, hipMemcpyDeviceToHost, st));
+    FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + j.wp_bytes, &j.dyn->adds, 8, hipMemcpyDeviceToHost, st));
+    FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + j.wp_bytes + 8, &j.dyn->error, 4, hipMemcpyDeviceToHost, st));
+    FK_HIP(ctx, hipEventRecord(tl.done, st));
+    FK_DBG_ST(ctx, st, "msm_bucket_reduce");
     return FK_OK;
 }
 
@@ -1168,7 +1226,6 @@ static int lane_stage(fk_ctx *ctx, MsmLane &ln, size_t bytes) {     // pinned st
 // the quotient's kernels, and the GPU decides what runs underneath what.
 template <class F>
 static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail_out, hipEvent_t ready, const KeyPre *pre = nullptr) {
-    using FC = typename ColdOf<F>::type;   // layout-identical field with an out-of-line multiply
     *tail_out = -1;
     if (n == 0) return FK_OK;
     if (n >= ((size_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: n too large");
@@ -1183,7 +1240,6 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
         const MsmPlan pm = make_plan(n, ctx->window_bits, true);
         if (pm.cb == pre->cb && pm.wide == pre->wide && pm.W == pre->W) { p = pm; merged = true; }
     }
-    const Affine<F> *d_lev = merged ? (const Affine<F> *)pre->lev : nullptr;
     // lane: the next one in turn, unless this call reuses the previous call's sort (B2 after B1).  With three lanes the
     // multiplication after the G2 one does not queue behind its long overflow / reduction tail (at 2^22 that tail was 5.4 ms
     // during which nothing else ran: 31 % of the proof).
@@ -1191,205 +1247,42 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
     const bool have_sort = reuse_sort && prev.st && prev.last_sort_scalars == (const void *)d_scalars && prev.last_sort_n == n && prev.last_sort_c == p.c && prev.last_merged == merged;
     const int li = have_sort ? ctx->lane_prev : ctx->lane_next;
     MsmLane &ln = ctx->lanes[li];
-    FK_TRY(lane_init(ctx, ln));
+    if (!ln.st) FK_SET_ERR(ctx, FK_ERR_HIP, "msm: the context's streams were not created");      // (streams_init: fk_init, fk_trim)
     // FK_MSM_LANES (experiment builds): fewer lanes -- never while pieces are deferred (sorts-first schedule): its deferred
     // accumulations and tails hold pointers into their lane's buffers, so every multiplication needs a lane of its own there
     static const int t_lanes = tune("FK_MSM_LANES", 0);
     const int n_lanes = (t_lanes >= 1 && t_lanes <= MSM_LANES && !ctx->defer_back && ctx->deferred.empty())
                             ? t_lanes : (ctx->lanes_in_use >= 2 && ctx->lanes_in_use <= MSM_LANES ? ctx->lanes_in_use : MSM_LANES);
     ctx->lane_prev = li; ctx->lane_next = (li + 1) % n_lanes;
-    hipStream_t st = ln.st;
-    hipStream_t ss = st;                      // the front of the multiplication runs on the lane's stream as well
-    if (ready) FK_HIP(ctx, hipStreamWaitEvent(ss, ready, 0));
+    if (ready) FK_HIP(ctx, hipStreamWaitEvent(ln.st, ready, 0));      // (the front of the multiplication runs on the lane's stream as well)
     else {
         FK_HIP(ctx, hipEventRecord(ln.ev_in, ctx->stream));        // scalars / bases produced on the main stream
-        FK_HIP(ctx, hipStreamWaitEvent(ss, ln.ev_in, 0));
+        FK_HIP(ctx, hipStreamWaitEvent(ln.st, ln.ev_in, 0));
     }
-    const size_t WB = (size_t)p.W * p.B;
-    const uint32_t WR = merged ? 1 : p.W;      // bucket sets to reduce
-    // bucket reduction: the flat form (up to 64 buckets per lane, then a double-and-add by the lane's offset).  A hierarchical form
-    // (8 buckets per lane, wave-level suffix sums) was built in round 2: a 2.5x shorter serial chain, 1.6x the additions, slower
-    // everywhere (171.5 -> 178.3 ms per proof at 2^25) -- removed in round 3.
-    const size_t wp_bytes = (size_t)WR * sizeof(Xyzz<F>);                      // ONE point per bucket set (folded on the device)
-    const size_t wp_dev_bytes = (size_t)WR * (p.nblk + 1) * sizeof(Xyzz<F>);  // ... behind the nblk partial sums of every set
-    // oversized buckets: at most OVER_MAX are tabled; their segment tasks are bounded by max(2048, W n / SEG_MAX) + one per bucket
-    const size_t max_tasks = std::max<size_t>(2048, (size_t)p.W * n / SEG_MAX) + OVER_MAX + 64;
-    // Growing a buffer frees the old one: everything queued on this lane must be finished first.
-    const uint32_t nseg = p.W * p.nhi;
-    const size_t max_tiles = (size_t)p.W * ((n + S2_TILE - 1) / S2_TILE) + nseg + 1;
-    struct Need { DevBuf *b; size_t bytes; };
-    const Need needs[] = {
-        {&ln.digits, (size_t)p.W * n * 4}, {&ln.sorted, (size_t)p.W * n * 4}, {&ln.totals, WB * 4}, {&ln.starts, WB * 4},
-        {&ln.perm, WB * 4 + SIZE_BINS * 4}, {&ln.overlist, OVER_MAX * sizeof(OverEntry) + sizeof(MsmDyn) + 64}, {have_sort ? &ln.buckets2 : &ln.buckets, WB * sizeof(Xyzz<F>)},
-        {&ln.tasktab, max_tasks * sizeof(Task) + OVER_MAX * sizeof(OverBucket) + 64}, {&ln.partials, max_tasks * sizeof(Xyzz<F>)},
-        {&ln.s2_cnt1, (size_t)p.W * p.nchunks * p.nhi * 4}, {&ln.s2_seg, ((size_t)nseg * 4 + 2) * 4}, {&ln.s2_cnt2, max_tiles * p.nlo * 4},
-        {&ln.s2_tmp_idx, (size_t)p.W * n * 4}, {&ln.s2_tmp_lo, (size_t)p.W * n * 2}};
-    bool grow = false;
-    for (const Need &nd : needs) grow = grow || nd.bytes > nd.b->cap;
-    if (grow) {
-        FK_HIP(ctx, hipStreamSynchronize(st));
-        for (const Need &nd : needs) FK_HIP(ctx, nd.b->reserve(nd.bytes));
-        if (!have_sort) ln.last_sort_scalars = nullptr;
-    }
-    FK_HIP(ctx, tl.d_wp.reserve(wp_dev_bytes));
-    if (wp_bytes + 16 > tl.h_cap) {         // + the additions counter and the error word
-        if (tl.h_wp) { FK_HIP(ctx, hipHostFree(tl.h_wp)); tl.h_wp = nullptr; tl.h_cap = 0; }
-        FK_HIP(ctx, hipHostMalloc(&tl.h_wp, wp_bytes + (wp_bytes >> 2) + 16, hipHostMallocDefault));
-        tl.h_cap = wp_bytes + (wp_bytes >> 2) + 16;
-    }
-    MsmDyn *dyn = (MsmDyn *)((char *)ln.overlist.p + OVER_MAX * sizeof(OverEntry));       // device-side state of this lane's sort
-    unsigned long long *d_adds = &dyn->adds;
-    Task *d_tasks = ln.tasktab.as<Task>();
-    OverBucket *d_obs = (OverBucket *)((char *)ln.tasktab.p + ((max_tasks * sizeof(Task) + 15) & ~(size_t)15));
-    uint32_t *digits = ln.digits.as<uint32_t>(), *sorted = ln.sorted.as<uint32_t>();
-    uint32_t *totals = ln.totals.as<uint32_t>(), *starts = ln.starts.as<uint32_t>();
-    Xyzz<F> *winparts = tl.d_wp.as<Xyzz<F>>();         // (the bucket buffer is bound in the back half, below)
-    uint32_t *perm = ln.perm.as<uint32_t>(), *size_bins = perm + WB;
-
+    MsmJob<F> job{};
+    job.ctx = ctx; job.p = p; job.ln = &ln; job.tl = &tl;
+    job.bases = d_bases; job.lev = merged ? (const Affine<F> *)pre->lev : nullptr; job.scalars = d_scalars;
+    job.n = n; job.merged = merged; job.have_sort = have_sort;
+    FK_TRY(msm_reserve(job));
+    // With a reused sort (B2 after B1) the lane's state and tables are still valid.
     if (!have_sort) {
-        ln.last_sort_scalars = nullptr;
-        hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)(((n + 1) / 2 + 63) / 64)), dim3(64), 0, ss, d_scalars, n, p.cb, p.wide, p.W, digits);
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG_ST(ctx, ss, "msm_digits");
-        FK_HIP(ctx, hipMemsetAsync(dyn, 0, sizeof(MsmDyn), ss));
-        uint32_t *cnt1 = ln.s2_cnt1.as<uint32_t>();
-        uint32_t *seg_size = ln.s2_seg.as<uint32_t>(), *seg_start = seg_size + nseg, *seg_tiles = seg_start + nseg, *tile_start = seg_tiles + nseg;
-        uint32_t *cnt2 = ln.s2_cnt2.as<uint32_t>(), *tmp_idx = ln.s2_tmp_idx.as<uint32_t>();
-        uint16_t *tmp_lo = ln.s2_tmp_lo.as<uint16_t>();
-        hipLaunchKernelGGL(s2_hist1_kernel, dim3(p.nchunks, p.W), dim3(SORT_THREADS), p.nhi * 4, ss, digits, n, p.chunk, p.nchunks, p.LB, p.nhi, cnt1);
-        hipLaunchKernelGGL(s2_prefix1_kernel, dim3(p.W), dim3(1024), p.nhi * 4, ss, cnt1, p.nchunks, p.nhi, seg_size, seg_start, seg_tiles);
-        hipLaunchKernelGGL(s2_tile_prefix_kernel, dim3(1), dim3(1024), 0, ss, seg_tiles, nseg, tile_start);
-#ifdef FK_S1_NT
-        if (tune("FK_S1_THIN", 1)) hipLaunchKernelGGL(s2_scatter1_thin_kernel, dim3(p.nchunks, p.W), dim3(FK_S1_NT), 0, ss, digits, n, p.chunk, p.nchunks, p.LB, p.nhi, cnt1, seg_start, tmp_idx, tmp_lo);
-        else
-#endif
-        hipLaunchKernelGGL(s2_scatter1_n1024_kernel, dim3(p.nchunks, p.W), dim3(1024), 0, ss, digits, n, p.chunk, p.nchunks, p.LB, p.nhi, cnt1, seg_start, tmp_idx, tmp_lo);
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG_ST(ctx, ss, "msm_sort_pass1");
-        // The second pass is launched over the host's BOUND on the tile count (every segment's last tile may be partial:
-        // W * ceil(n / tile) + #segments); workgroups beyond the actual count leave at once.  Reading the count back cost a
-        // host round trip in the middle of every sort.
-        const uint32_t n_tiles = (uint32_t)max_tiles;
-        {
-            hipLaunchKernelGGL(s2_hist2_kernel, dim3(n_tiles), dim3(256), p.nlo * 4, ss, tmp_lo, n, p.nhi, p.nlo, tile_start, nseg, seg_start, seg_size, cnt2);
-        }
-        hipLaunchKernelGGL(s2_prefix2_kernel, dim3((nseg + 3) / 4), dim3(256), 0, ss, cnt2, nseg, p.nhi, p.nlo, p.B, tile_start, seg_start, p.cap ? p.cap : 1u, totals, starts, dyn);
-        {
-            if (p.nlo <= 1024) hipLaunchKernelGGL(s2_scatter2_kernel<1024>, dim3(n_tiles), dim3(1024), 0, ss, tmp_idx, tmp_lo, n, p.nhi, p.nlo, p.B, tile_start, nseg, seg_start, seg_size, cnt2, starts, sorted);
-            else if (p.nlo <= 2048) hipLaunchKernelGGL(s2_scatter2_kernel<2048>, dim3(n_tiles), dim3(1024), 0, ss, tmp_idx, tmp_lo, n, p.nhi, p.nlo, p.B, tile_start, nseg, seg_start, seg_size, cnt2, starts, sorted);
-            else hipLaunchKernelGGL(s2_scatter2_kernel<4096>, dim3(n_tiles), dim3(1024), 0, ss, tmp_idx, tmp_lo, n, p.nhi, p.nlo, p.B, tile_start, nseg, seg_start, seg_size, cnt2, starts, sorted);
-        }
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG_ST(ctx, ss, "msm_sort_pass2");
-        ln.last_sort_scalars = (const void *)d_scalars; ln.last_sort_n = n; ln.last_sort_c = p.c; ln.last_merged = merged;
+        FK_TRY(queue_sort(job));
+        FK_TRY(queue_size_order(job));
+        FK_HIP(ctx, hipEventRecord(ln.ev_sorted, ln.st)); ln.ev_sorted_valid = true;
     }
-    // oversized buckets (skewed scalars), size ordering: all on the device (MsmDyn) -- nothing below waits for the host.  With a
-    // reused sort (B2 after B1) the lane's state and tables are still valid.
-    if (!have_sort) {
-        static const int t_many = tune("FK_MSM_OVER_MANY", 2048);
-        // "few": every oversized bucket costs a wave per segment plus a 256-lane fold workgroup -- with 4e5 of them, what round 1's
-        // WB / 64 allowed at 2^25, the overflow + fold kernels took 70 ms of a proof whose witness held each value 341 times
-        const uint32_t many = (uint32_t)std::min<size_t>(std::max<size_t>((size_t)t_many, WB / 8192), OVER_MAX - 64);
-        hipLaunchKernelGGL(msm_cap_kernel, dim3(1), dim3(64), 0, ss, dyn, p.cap ? p.cap : 1u, many);
-        hipLaunchKernelGGL(msm_over_list_kernel, dim3((unsigned)((WB + 255) / 256)), dim3(256), 0, ss, totals, WB, ln.overlist.as<OverEntry>(), dyn);
-        hipLaunchKernelGGL(msm_tasks_kernel, dim3(1), dim3(1024), 0, ss, ln.overlist.as<OverEntry>(), dyn, p.B, merged ? 1 : 0, d_tasks, (uint32_t)max_tasks, d_obs);
-        // size-ordered bucket -> lane assignment
-        FK_HIP(ctx, hipMemsetAsync(size_bins, 0, SIZE_BINS * 4, ss));
-        if (merged) {     // one bucket set: order its B buckets by their length over all windows (perm[0, B); lengths kept behind it)
-            uint32_t *mt = perm + p.B;
-            hipLaunchKernelGGL(msm_merge_totals_kernel, dim3(std::min<uint32_t>((p.B + 255) / 256, 1024)), dim3(256), 0, ss, totals, p.B, p.W, dyn, mt, d_adds);
-            hipLaunchKernelGGL(msm_size_hist_kernel, dim3((unsigned)std::min<size_t>((p.B + 255) / 256, 1024)), dim3(256), 0, ss, mt, (size_t)p.B, dyn, p.W, size_bins, (unsigned long long *)nullptr);
-            hipLaunchKernelGGL(msm_size_scan_kernel, dim3(1), dim3(SIZE_BINS), 0, ss, size_bins);
-            hipLaunchKernelGGL(msm_size_scatter_kernel, dim3((unsigned)((p.B + 1023) / 1024)), dim3(1024), 0, ss, mt, (size_t)p.B, dyn, p.W, size_bins, perm);
-        } else {
-            hipLaunchKernelGGL(msm_size_hist_kernel, dim3((unsigned)std::min<size_t>((WB + 255) / 256, 1024)), dim3(256), 0, ss, totals, WB, dyn, 1u, size_bins, d_adds);
-            hipLaunchKernelGGL(msm_size_scan_kernel, dim3(1), dim3(SIZE_BINS), 0, ss, size_bins);
-            hipLaunchKernelGGL(msm_size_scatter_kernel, dim3((unsigned)((WB + 1023) / 1024)), dim3(1024), 0, ss, totals, WB, dyn, 1u, size_bins, perm);
-        }
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG_ST(ctx, ss, "msm_size_order");
-        if (ctx->debug) {
-            MsmDyn h{};
-            FK_HIP(ctx, hipMemcpy(&h, dyn, sizeof h, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[fk] msm n=%zu c=%u (W=%u: %u x %u bits + %u x %u bits) cap=%u (plan %u): %u oversized buckets, %u tasks of %u entries, %u fold groups\n", n, p.c,
-                    p.W, p.wide, p.cb + 1, p.W - p.wide, p.cb, h.cap, p.cap, h.n_over, h.n_tasks, h.seg, h.n_obs);
-            fflush(stderr);
-        }
-    }
-
     // ---- from here on nothing waits for the host
-    if (!have_sort) { FK_HIP(ctx, hipEventRecord(ln.ev_sorted, ss)); ln.ev_sorted_valid = true; }
-    tl.active = true; tl.cb = p.cb; tl.wide = p.wide; tl.W = WR; tl.nblk = 1;     // merged: one "window" of weight 1
+    tl.active = true; tl.cb = p.cb; tl.wide = p.wide; tl.W = job.WR; tl.nblk = 1;     // merged: one "window" of weight 1
     *tail_out = ti;
     // The back of the multiplication in two pieces -- the accumulation, and the tail (oversized buckets, reduction, download) --
     // queued now, or by msm_run_deferred (ctx->defer_back): all accumulations first, then all tails, so that on the B pair's lane
     // the G2 accumulation follows the G1 one at once and both tails come behind (B2 has a bucket buffer of its own for that).
-    MsmLane *lnp = &ln; MsmTail *tlp = &tl;
-    // FK_MSM_LAZY (default 1): accumulators in the lazily reduced form [0, 2p) (Walker<F, 2>); 0 = canonical after every product
-    static const int t_lazy = tune("FK_MSM_LAZY", 1);
-    constexpr bool IS_G1 = std::is_same<F, Fq>::value;
-    const bool lazy = t_lazy != 0;
-    constexpr int MINW_ = IS_G1 ? 4 : 2;
-    // bound late (inside the pieces): a multiplication begun on this lane in between may have GROWN a buffer, i.e. moved it
-    auto bucket_buf = [=]() -> Xyzz<F> * { return (have_sort ? lnp->buckets2 : lnp->buckets).template as<Xyzz<F>>(); };
-    auto back_acc = [=]() -> int {
-        Xyzz<F> *buckets = bucket_buf();
-        std::vector<EventPair> &evv = (sizeof(F) == sizeof(Fq)) ? ctx->ev_acc : ctx->ev_acc2;
-        FK_TRY(stats_begin(ctx, evv, (uint64_t)n, st));
-        if (merged) {
-            if (lazy) hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_merged_kernel<F, MINW_, 2>), dim3((p.B + 255) / 256), dim3(256), 0, st, d_bases, d_lev, sorted, n,
-                                              starts, totals, p.B, p.W, dyn, perm, perm + p.B, buckets);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_merged_kernel<F, MINW_, 0>), dim3((p.B + 255) / 256), dim3(256), 0, st, d_bases, d_lev, sorted, n,
-                                    starts, totals, p.B, p.W, dyn, perm, perm + p.B, buckets);
-        } else {
-            if (lazy) hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_kernel<F, MINW_, 2>), dim3((unsigned)((WB + 255) / 256)), dim3(256), 0, st, d_bases, sorted, n,
-                                              starts, totals, p.B, p.W, dyn, perm, buckets);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_kernel<F, MINW_, 0>), dim3((unsigned)((WB + 255) / 256)), dim3(256), 0, st, d_bases, sorted, n,
-                                    starts, totals, p.B, p.W, dyn, perm, buckets);
-        }
-        FK_HIP(ctx, hipGetLastError());
-        FK_TRY(stats_end(ctx, evv, st));
-        if (!ctx->ev_acc_done) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_acc_done, hipEventDisableTiming));
-        FK_HIP(ctx, hipEventRecord(ctx->ev_acc_done, st)); ctx->ev_acc_done_valid = true;
-        FK_DBG_ST(ctx, st, "msm_accumulate");
-        return FK_OK;
-    };
-    auto back_tail = [=]() -> int {
-        MsmLane &ln = *lnp; MsmTail &tl = *tlp;
-        Xyzz<F> *buckets = bucket_buf();
-        // oversized buckets: fixed grids looping over the device-built tables (they leave at once when there is nothing to do)
-        if (lazy) hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_kernel<F, FC, 2>), dim3(2048), dim3(64), 0, st,
-                                          d_bases, d_lev, sorted, n, starts, totals, p.B, dyn, d_tasks, ln.partials.as<Xyzz<FC>>());
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_kernel<F, FC, 0>), dim3(2048), dim3(64), 0, st,
-                                d_bases, d_lev, sorted, n, starts, totals, p.B, dyn, d_tasks, ln.partials.as<Xyzz<FC>>());
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG_ST(ctx, st, "msm_overflow");
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_fold_kernel<F>), dim3(256), dim3(256), 0, st, d_obs, dyn, ln.partials.as<Xyzz<F>>(), buckets);
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG_ST(ctx, st, "msm_overflow_fold");
-        const Xyzz<F> *wp_src = winparts;
-        {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_bucket_reduce_kernel<F>), dim3(p.nblk, WR), dim3(256), 0, st,
-                               buckets, p.B, p.L, p.T, p.nblk, winparts);
-            Xyzz<F> *folded = winparts + (size_t)WR * p.nblk;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_fold_partials_kernel<F>), dim3(WR), dim3(256), 0, st, winparts, p.nblk, folded);
-            wp_src = folded;
-        }
-        FK_HIP(ctx, hipGetLastError());
-        FK_HIP(ctx, hipMemcpyAsync(tl.h_wp, wp_src, wp_bytes, hipMemcpyDeviceToHost, st));
-        FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + wp_bytes, d_adds, 8, hipMemcpyDeviceToHost, st));
-        FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + wp_bytes + 8, &dyn->error, 4, hipMemcpyDeviceToHost, st));
-        FK_HIP(ctx, hipEventRecord(tl.done, st));
-        FK_DBG_ST(ctx, st, "msm_bucket_reduce");
-        return FK_OK;
-    };
     if (ctx->defer_back) {
-        ctx->deferred.push_back(back_acc);
-        ctx->deferred_tails.push_back(back_tail);
+        ctx->deferred.push_back([job] { return queue_accumulate<F>(job); });
+        ctx->deferred_tails.push_back([job] { return queue_tail<F>(job); });
         return FK_OK;
     }
-    FK_TRY(back_acc());
-    return back_tail();
+    FK_TRY(queue_accumulate<F>(job));
+    return queue_tail<F>(job);
 }
 
 // queues the deferred pieces in the order their multiplications were begun -- all accumulations, then all tails (the lane
@@ -1457,7 +1350,6 @@ void msm_release(fk_ctx *ctx) {
         for (DevBuf *b : {&ln.digits, &ln.sorted, &ln.totals, &ln.starts, &ln.perm, &ln.overlist, &ln.tasktab, &ln.partials, &ln.s2_cnt1, &ln.s2_seg,
                           &ln.s2_cnt2, &ln.s2_tmp_idx, &ln.s2_tmp_lo, &ln.buckets, &ln.buckets2})
             b->release();
-        if (ln.h_stage) (void)hipHostFree(ln.h_stage);
         if (ln.ev_in) (void)hipEventDestroy(ln.ev_in);
         if (ln.ev_sorted) (void)hipEventDestroy(ln.ev_sorted);
         if (ln.st) (void)hipStreamDestroy(ln.st);

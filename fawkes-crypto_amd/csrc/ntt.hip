@@ -67,9 +67,8 @@ struct PassArgs {
 
 // The passes compute in the lazily reduced form FrL ([0, 2r): no conditional subtraction behind a product, field.hpp); what
 // they read from memory (data, tables) is canonical, hence valid, and what they store is made canonical again.
-// (FL = Fr itself: the canonical form, FK_NTT_LAZY=0.)
+// (Butterflies in the canonical form, FL = Fr, were the round-1 kernel: 190.5 against 190.0 ms per proof in round 2, no longer instantiated.)
 template <class FL> static __device__ __forceinline__ FL ldl_(const Fr &x) { FL r; for (int i = 0; i < 8; i++) r.v[i] = x.v[i]; return r; }
-static __device__ __forceinline__ Fr canon(const Fr &x) { return x; }
 template <class FL>
 static __device__ __forceinline__ void lds_put(uint4 *p0, uint4 *p1, uint32_t e, const FL &v) {
     p0[e] = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
@@ -392,8 +391,7 @@ static int ntt_exec(fk_ctx *ctx, NttDomain *d, const NttOp &op, const Fr *in, Fr
         if (op.post) { a.post_lo = op.post->lo; a.post_hi = op.post->hi; a.post_full = op.post->full; }
         const uint64_t nblk = ((uint64_t)1 << (d->log_n - deg)) >> logC;
         const size_t lds_bytes = (size_t)2 * sizeof(uint4) << (deg + logC);
-        static const int t_lazy = tune("FK_NTT_LAZY", 1);     // 0: butterflies in the canonical form (the round-1 kernel)
-        void (*kern)(PassArgs) = t_lazy ? ntt_pass_kernel<FrL> : ntt_pass_kernel<Fr>;
+        void (*kern)(PassArgs) = ntt_pass_kernel<FrL>;
         FK_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         FK_TRY(stats_begin(ctx, ctx->ev_ntt, (uint64_t)1 << d->log_n));
         // one lane per two butterflies (the kernel issues the field products of a pair as dual chains)
