@@ -148,7 +148,8 @@ def check(text):
     return n, bad
 
 
-def main():
+def main(out=OUT):
+    """writes the generated text to `out`; returns (reads checked against the hazard rule, violations) -- violations is 0, or nothing is written"""
     o = ['// GENERATED by tools/gen_addsub.py -- do not edit.',
          '// Modular addition / subtraction as carry chains (primary chain + lagging correction chain + select), gfx950',
          '// inline asm; see the generator for the schedule and the SGPR-carry hazard rule it obeys.']
@@ -164,9 +165,12 @@ def main():
     n, bad = check(text)
     if bad or n == 0:
         raise SystemExit('hazard rule violated in %d of %d carry / mask reads' % (bad, n))
-    open(OUT, 'w').write(text)
-    print('wrote %s (%d carry / mask reads checked against the SGPR hazard rule, 0 violations)' % (os.path.normpath(OUT), n))
+    with open(out, 'w') as f:
+        f.write(text)
+    print('wrote %s (%d carry / mask reads checked against the SGPR hazard rule, 0 violations)' % (os.path.normpath(out), n))
+    return n, bad
 
 
 if __name__ == '__main__':
-    main()
+    import sys
+    main(*sys.argv[1:2])

@@ -329,7 +329,8 @@ def check(text):
     return n, bad
 
 
-def main():
+def main(out=OUT):
+    """writes the generated text to `out`; returns (reads checked against the hazard rule, violations) -- violations is 0, or nothing is written"""
     o = ['// GENERATED by tools/gen_mont_mul.py -- do not edit.',
          '// Product-scanning Montgomery multiplication, 8 x u32 limbs, gfx950 inline asm (see the generator for the',
          '// schedule and the SGPR-carry hazard rule it obeys).']
@@ -344,9 +345,12 @@ def main():
     n, bad = check(text)
     if bad:
         raise SystemExit('hazard rule violated in %d of %d v_addc' % (bad, n))
-    open(OUT, 'w').write(text)
-    print('wrote %s (%d v_addc checked against the SGPR-carry hazard rule, 0 violations)' % (os.path.normpath(OUT), n))
+    with open(out, 'w') as f:
+        f.write(text)
+    print('wrote %s (%d v_addc checked against the SGPR-carry hazard rule, 0 violations)' % (os.path.normpath(out), n))
+    return n, bad
 
 
 if __name__ == '__main__':
-    main()
+    import sys
+    main(*sys.argv[1:2])
