@@ -46,6 +46,10 @@ EXPORTED_SYMBOLS = [
     'fk_multi_key_load', 'fk_multi_key_load_bellman', 'fk_multi_setup', 'fk_multi_setup_tiled', 'fk_multi_key_free', 'fk_multi_key_shard',
     'fk_multi_r1cs_load', 'fk_multi_r1cs_load_tiled', 'fk_multi_r1cs_load_gates', 'fk_multi_r1cs_free', 'fk_multi_r1cs_replica',
     'fk_multi_prove_r1cs', 'fk_multi_prove_r1cs_submit', 'fk_multi_prove_r1cs_wait',
+    'fk_poseidon_params_new', 'fk_poseidon_params_load', 'fk_poseidon_params_get', 'fk_poseidon_free',
+    'fk_poseidon_hash_batch', 'fk_poseidon_hash_batch_dev', 'fk_poseidon_sponge_batch',
+    'fk_poseidon_merkle_tree_dev', 'fk_poseidon_merkle_root', 'fk_poseidon_merkle_proofs_dev',
+    'fk_poseidon_merkle_proof_roots', 'fk_poseidon_merkle_proof_roots_dev',
 ]
 
 _ERR = {1: 'FK_ERR_BAD_ARG', 2: 'FK_ERR_DOMAIN_TOO_LARGE (bellman: PolynomialDegreeTooLarge)',
@@ -133,6 +137,8 @@ def load_library():
         lib.fk_multi_key_shard.argtypes = [C.c_void_p, C.c_int]
         lib.fk_multi_r1cs_replica.restype = C.c_void_p
         lib.fk_multi_r1cs_replica.argtypes = [C.c_void_p, C.c_int]
+        lib.fk_poseidon_free.argtypes = [C.c_void_p]
+        lib.fk_poseidon_free.restype = None
         _LIB = lib
     return _LIB
 
@@ -676,6 +682,145 @@ class HostVk:
             pass
 
 
+_FR_RINV = pow(1 << 256, -1, FR_MODULUS)
+
+
+def _fr_rows(values, n=None):
+    """(n, 4) u64 Montgomery limbs from a limb array (last axis 4, dtype uint64) or from canonical ints (any nesting, flattened)"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+        a = np.ascontiguousarray(values).reshape(-1, 4)
+    else:
+        flat = np.asarray(values, dtype=object).reshape(-1)
+        a = np.zeros((len(flat), 4), np.uint64)
+        for i, v in enumerate(flat):
+            v = int(v)
+            if not 0 <= v < FR_MODULUS:
+                raise ValueError('field element out of range: %d' % v)
+            a[i] = int_to_limbs((v << 256) % FR_MODULUS)
+    if n is not None and a.shape[0] != n:
+        raise ValueError('expected %d field elements, got %d' % (n, a.shape[0]))
+    return a
+
+
+def _fr_ints(limbs):
+    """canonical ints of (n, 4) Montgomery limbs"""
+    return [limbs_to_int(row) * _FR_RINV % FR_MODULUS for row in np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)]
+
+
+class PoseidonParams:
+    """native/poseidon.rs:15-49: PoseidonParams::new_with_salt(t, f, p, salt), generated by the library on the host (fk_poseidon_params_new;
+    no GPU needed).  `.c` ((f + p) rows of t) and `.m` (t rows of t) are canonical ints."""
+
+    def __init__(self, t, f, p, salt='', _handle=None):
+        self.lib = load_library()
+        self.handle = None
+        if _handle is None:
+            _handle = C.c_void_p()
+            rc = self.lib.fk_poseidon_params_new(C.c_uint32(t), C.c_uint32(f), C.c_uint32(p), C.c_char_p(salt.encode()), C.byref(_handle))
+            if rc != 0:
+                raise FkError(rc, (self.lib.fk_last_error(None) or b'').decode())
+        self.handle = _handle
+        self.t, self.f, self.p = int(t), int(f), int(p)
+
+    @classmethod
+    def from_arrays(cls, t, f, p, c, m):
+        """fk_poseidon_params_load: c = (f + p) * t constants, m = t * t matrix entries (row major), canonical ints or Montgomery limb arrays"""
+        lib = load_library()
+        h = C.c_void_p()
+        if not (isinstance(t, int) and isinstance(f, int) and isinstance(p, int)) or min(t, f, p) < 0 or max(t, f, p) >= 1 << 32:
+            raise FkError(1, 'poseidon: t, f, p must be small non-negative integers')
+        ca, ma = _fr_rows(c, (f + p) * t), _fr_rows(m, t * t)
+        rc = lib.fk_poseidon_params_load(C.c_uint32(t), C.c_uint32(f), C.c_uint32(p), _vp(ca), _vp(ma), C.byref(h))
+        if rc != 0:
+            raise FkError(rc, (lib.fk_last_error(None) or b'').decode())
+        return cls(t, f, p, _handle=h)
+
+    def limbs(self):
+        """(c, m) as Montgomery limb arrays of shape (f + p, t, 4) and (t, t, 4): what fk_poseidon_params_get returns"""
+        dims = (C.c_uint32 * 3)()
+        c = np.zeros((self.f + self.p, self.t, 4), np.uint64)
+        m = np.zeros((self.t, self.t, 4), np.uint64)
+        rc = self.lib.fk_poseidon_params_get(self.handle, dims, _vp(c), _vp(m))
+        if rc != 0 or tuple(dims) != (self.t, self.f, self.p):
+            raise FkError(rc or 1, 'fk_poseidon_params_get')
+        return c, m
+
+    @property
+    def c(self):
+        v = _fr_ints(self.limbs()[0])
+        return [v[i * self.t:(i + 1) * self.t] for i in range(self.f + self.p)]
+
+    @property
+    def m(self):
+        v = _fr_ints(self.limbs()[1])
+        return [v[i * self.t:(i + 1) * self.t] for i in range(self.t)]
+
+    def free(self):
+        if getattr(self, 'handle', None):
+            self.lib.fk_poseidon_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MerkleTree:
+    """A Poseidon Merkle tree resident in device memory (Context.merkle_tree): 2^(depth + 1) - 1 nodes, the leaves (zero-padded to
+    2^depth) first, the root last."""
+
+    def __init__(self, ctx, d_nodes, depth, n_leaves):
+        self.ctx, self.d_nodes, self.depth, self.n_leaves = ctx, d_nodes, depth, n_leaves
+        self._root = None
+
+    @property
+    def n_nodes(self):
+        return (2 << self.depth) - 1
+
+    @property
+    def root(self):
+        if self._root is None:
+            limbs = self.ctx.download(self.d_nodes + 32 * (self.n_nodes - 1), 32, np.uint64)
+            self._root = _fr_ints(limbs)[0]
+        return self._root
+
+    def nodes(self):
+        """every node as Montgomery limbs, (2^(depth + 1) - 1, 4)"""
+        return self.ctx.download(self.d_nodes, 32 * self.n_nodes, np.uint64).reshape(-1, 4)
+
+    def proofs(self, indices):
+        """(siblings, indices): siblings[i] = the depth siblings of leaf indices[i], leaf level first, canonical ints"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        n = idx.shape[0]
+        if n == 0:
+            return [], []
+        ctx = self.ctx
+        d_idx = ctx.dev_alloc(8 * n)
+        d_sib = ctx.dev_alloc(max(32 * n * self.depth, 32))
+        try:
+            ctx.upload(d_idx, idx)
+            ctx._ck(ctx.lib.fk_poseidon_merkle_proofs_dev(ctx.handle, C.c_void_p(self.d_nodes), C.c_uint32(self.depth), C.c_void_p(d_idx), C.c_size_t(n),
+                                                          C.c_void_p(d_sib)))
+            flat = _fr_ints(ctx.download(d_sib, 32 * n * self.depth, np.uint64)) if self.depth else []
+        finally:
+            ctx.dev_free(d_idx)
+            ctx.dev_free(d_sib)
+        return [flat[i * self.depth:(i + 1) * self.depth] for i in range(n)], [int(i) for i in idx]
+
+    def free(self):
+        if getattr(self, 'd_nodes', None) and getattr(self.ctx, 'handle', None):
+            self.ctx.dev_free(self.d_nodes)
+        self.d_nodes = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU (one process per GPU for multi-GPU runs).  Raises FkError if no GPU is usable."""
 
@@ -1123,6 +1268,84 @@ class Context:
 
     def dev_copy(self, dst, src, nbytes):
         self._ck(self.lib.fk_dev_copy(self.handle, C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes)))
+
+    # ---- Poseidon (native/poseidon.rs): inputs as canonical ints give ints back, Montgomery limb arrays (dtype uint64) give limbs back
+    def poseidon(self, params, inputs):
+        """poseidon(inputs[i], params) for every row: an (n, k, 4) / (n, 4 k) limb array or a list of n tuples of k ints, 0 < k < t"""
+        as_limbs = isinstance(inputs, np.ndarray) and inputs.dtype == np.uint64
+        n = len(inputs)
+        if as_limbs:
+            k = int(np.prod(inputs.shape[1:])) // 4 if n else 1
+        else:
+            k = len(inputs[0]) if n else 1
+            if any(len(row) != k for row in inputs):
+                raise ValueError('poseidon: every row takes the same number of inputs')
+        a = _fr_rows(inputs, n * k)
+        out = np.zeros((n, 4), np.uint64)
+        self._ck(self.lib.fk_poseidon_hash_batch(self.handle, params.handle, _vp(a), C.c_uint32(k), C.c_size_t(n), _vp(out)))
+        return out if as_limbs else _fr_ints(out)
+
+    def poseidon_dev(self, params, d_inputs, n_inputs, n, d_out):
+        self._ck(self.lib.fk_poseidon_hash_batch_dev(self.handle, params.handle, C.c_void_p(d_inputs), C.c_uint32(n_inputs), C.c_size_t(n), C.c_void_p(d_out)))
+
+    def poseidon_sponge(self, params, messages):
+        """poseidon_sponge(messages[i], params) for n messages of one length: (n, len, 4) limbs or a list of n tuples of ints"""
+        as_limbs = isinstance(messages, np.ndarray) and messages.dtype == np.uint64
+        n = len(messages)
+        if as_limbs:
+            ln = int(np.prod(messages.shape[1:])) // 4 if n else 0
+        else:
+            ln = len(messages[0]) if n else 0
+            if any(len(row) != ln for row in messages):
+                raise ValueError('poseidon_sponge: one call takes messages of one length')
+        a = _fr_rows(messages, n * ln) if n * ln else None
+        out = np.zeros((n, 4), np.uint64)
+        self._ck(self.lib.fk_poseidon_sponge_batch(self.handle, params.handle, _vp(a), C.c_uint64(ln), C.c_size_t(n), _vp(out)))
+        return out if as_limbs else _fr_ints(out)
+
+    def merkle_tree_dev(self, params, d_leaves, n_leaves, d_nodes):
+        self._ck(self.lib.fk_poseidon_merkle_tree_dev(self.handle, params.handle, C.c_void_p(d_leaves), C.c_uint64(n_leaves), C.c_void_p(d_nodes)))
+
+    def merkle_tree(self, params, leaves):
+        """the whole tree over `leaves` (zero-padded to a power of two), kept in device memory -> MerkleTree"""
+        a = _fr_rows(leaves)
+        n = a.shape[0]
+        depth = max(n - 1, 0).bit_length()
+        d_nodes = self.dev_alloc(32 * ((2 << depth) - 1))
+        try:
+            if n:
+                self.upload(d_nodes, a)
+            self.merkle_tree_dev(params, d_nodes, n, d_nodes)
+            self.sync()
+        except Exception:
+            self.dev_free(d_nodes)
+            raise
+        return MerkleTree(self, d_nodes, depth, n)
+
+    def merkle_root(self, params, leaves):
+        """poseidon_merkle_tree_root(leaves, params)"""
+        as_limbs = isinstance(leaves, np.ndarray) and leaves.dtype == np.uint64
+        a = _fr_rows(leaves)
+        out = np.zeros((1, 4), np.uint64)
+        self._ck(self.lib.fk_poseidon_merkle_root(self.handle, params.handle, _vp(a), C.c_uint64(a.shape[0]), _vp(out)))
+        return out[0] if as_limbs else _fr_ints(out)[0]
+
+    def merkle_proof_roots(self, params, leaves, siblings, indices, depth):
+        """poseidon_merkle_proof_root for n proofs: siblings[i] holds `depth` elements (leaf level first), bit j of indices[i] is path[j]"""
+        as_limbs = isinstance(leaves, np.ndarray) and leaves.dtype == np.uint64
+        la = _fr_rows(leaves)
+        n = la.shape[0]
+        sa = _fr_rows(siblings, n * depth) if n * depth else None
+        ia = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        if ia.shape[0] != n:
+            raise ValueError('merkle_proof_roots: one index per leaf')
+        out = np.zeros((n, 4), np.uint64)
+        self._ck(self.lib.fk_poseidon_merkle_proof_roots(self.handle, params.handle, _vp(la), _vp(sa), _vp(ia), C.c_uint32(depth), C.c_size_t(n), _vp(out)))
+        return out if as_limbs else _fr_ints(out)
+
+    def merkle_proof_roots_dev(self, params, d_leaves, d_siblings, d_indices, depth, n, d_out):
+        self._ck(self.lib.fk_poseidon_merkle_proof_roots_dev(self.handle, params.handle, C.c_void_p(d_leaves), C.c_void_p(d_siblings), C.c_void_p(d_indices),
+                                                             C.c_uint32(depth), C.c_size_t(n), C.c_void_p(d_out)))
 
 
 class _MultiHandle:

@@ -557,6 +557,46 @@ int fk_verify(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uint64_t *inp
 int fk_verify_batch_dev(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uint64_t *inputs, uint32_t n_inputs,
                         const uint8_t *proofs, uint32_t count, uint8_t *accept);
 
+/* ---------------------------------------------------------------- Poseidon on the device (witness side)
+ * native/poseidon.rs next to the prover: PoseidonParams::new_with_salt, poseidon, poseidon_sponge, poseidon_merkle_proof_root and
+ * poseidon_merkle_tree_root, one hash per GPU lane.  Elements are Montgomery LE limbs like everywhere in this header; results are
+ * canonical field elements, so every output is byte-identical to the reference's.  An fk_poseidon is host memory only (no GPU, no
+ * context; read-only once made, so several contexts may hash with it); kernels are built for t = 2..6 and 8, any other t in 2..8 is
+ * FK_ERR_UNSUPPORTED at the first hash.  The params_* functions leave their message in fk_last_error(NULL).
+ *   fk_poseidon_params_new   the reference's generator: ChaCha20 keyed with Keccak-256("fawkes_poseidon(t=..,f=..,p=..,salt=..)"), a
+ *                            sample of four u64 with the top two bits shaved is accepted below r and IS the Montgomery image; c first,
+ *                            (f + p) x t, then x[t], y[t]; m[i][j] = 1 / (x[i] + y[j]).  salt may be NULL (= "").
+ *   fk_poseidon_params_load  (f + p) x t constants and t x t matrix entries, row major.  A limb image >= r is FK_ERR_FORMAT; t outside
+ *                            2..8 or f + p == 0 is FK_ERR_BAD_ARG.
+ *   fk_poseidon_params_get   dims = t, f, p; c / m (either may be NULL) receive the arrays fk_poseidon_params_load takes. */
+typedef struct fk_poseidon fk_poseidon;
+int fk_poseidon_params_new(uint32_t t, uint32_t f, uint32_t p, const char *salt, fk_poseidon **out);
+int fk_poseidon_params_load(uint32_t t, uint32_t f, uint32_t p, const uint64_t *c, const uint64_t *m, fk_poseidon **out);
+int fk_poseidon_params_get(const fk_poseidon *params, uint32_t dims[3], uint64_t *c, uint64_t *m);
+void fk_poseidon_free(fk_poseidon *params);
+/* poseidon(inputs, params) n times: hash i reads the n_inputs consecutive elements inputs[i * n_inputs ..], the rest of the state is
+ * zero, out[i] = state[0] after the permutation.  0 < n_inputs < t, else FK_ERR_BAD_ARG; n == 0 is a no-op. */
+int fk_poseidon_hash_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *inputs, uint32_t n_inputs, size_t n, uint64_t *out);
+int fk_poseidon_hash_batch_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_inputs, uint32_t n_inputs, size_t n, void *d_out);
+/* poseidon_sponge n times over messages of one length: message i is inputs[i * len ..]; the absorbed stream is Fr(len) followed by the
+ * message, taken t - 1 elements at a time, each chunk ADDED into state[0 .. chunk) before a permutation.  len == 0 absorbs the length
+ * word alone (inputs may then be NULL). */
+int fk_poseidon_sponge_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *inputs, uint64_t len, size_t n, uint64_t *out);
+/* poseidon_merkle_tree_root with the whole tree kept.  L = ceil(log2 n_leaves); d_nodes holds 2^(L + 1) - 1 elements: level 0 = the
+ * leaves, zero-padded to 2^L, then the higher levels in order, the root last (n_leaves == 1: L = 0, the root IS the leaf).  d_leaves
+ * may be d_nodes itself.  t = 3 parameters only; t != 3 or n_leaves == 0 is FK_ERR_BAD_ARG.  _dev is asynchronous on the library's stream. */
+int fk_poseidon_merkle_tree_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_leaves, uint64_t n_leaves, void *d_nodes);
+int fk_poseidon_merkle_root(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *leaves, uint64_t n_leaves, uint64_t *out_root);
+/* The `depth` siblings (leaf level first) of n leaves of a built tree of 2^depth leaves: d_siblings[i * depth + j], d_indices n x u64.
+ * An index >= 2^depth is FK_ERR_BAD_ARG: it is found on the device, reads nothing and leaves zeros in its row.  Blocks until done. */
+int fk_poseidon_merkle_proofs_dev(fk_ctx *ctx, const void *d_nodes, uint32_t depth, const void *d_indices, size_t n, void *d_siblings);
+/* poseidon_merkle_proof_root n times: at level j bit j of indices[i] picks poseidon([sibling, root]) (set) or poseidon([root, sibling]);
+ * bits from `depth` up are not looked at.  siblings: n x depth, proof-major.  depth <= 64; depth == 0 gives the leaf.  t = 3 only. */
+int fk_poseidon_merkle_proof_roots(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *leaves, const uint64_t *siblings,
+                                   const uint64_t *indices, uint32_t depth, size_t n, uint64_t *out);
+int fk_poseidon_merkle_proof_roots_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_leaves, const void *d_siblings,
+                                       const void *d_indices, uint32_t depth, size_t n, void *d_out);
+
 /* Kernel timing measured with HIP events on the library's stream since the last reset, summed over
  * launches.  which: 0 = msm_accumulate_kernel<Fq> (G1 bucket accumulation; units = points per launch),
  * 1 = msm_accumulate_kernel<Fq2> (G2), 2 = ntt_pass_kernel (units = elements per pass); 3 / 4 = the same kernels as 0 / 1

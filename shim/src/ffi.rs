@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fk_multi { _p: [u8; 0] }
 #[repr(C)] pub struct fk_multi_key { _p: [u8; 0] }
 #[repr(C)] pub struct fk_multi_r1cs { _p: [u8; 0] }
+#[repr(C)] pub struct fk_poseidon { _p: [u8; 0] }
 
 pub const FK_OK: c_int = 0;
 pub const FK_PROOF_BYTES: usize = 256;
@@ -77,4 +78,21 @@ extern "C" {
     pub fn fk_verify(ctx: *mut fk_ctx, vk: *const u8, vk_len: usize, inputs: *const u64, n_inputs: u32, proof: *const u8, accept: *mut c_int) -> c_int;
     pub fn fk_verify_batch_dev(ctx: *mut fk_ctx, vk: *const u8, vk_len: usize, inputs: *const u64, n_inputs: u32, proofs: *const u8,
                                count: u32, accept: *mut u8) -> c_int;
+
+    // Poseidon on the device (native/poseidon.rs: PoseidonParams::new_with_salt, poseidon, poseidon_sponge, poseidon_merkle_tree_root,
+    // poseidon_merkle_proof_root).  Elements are `Num<Fr>` images (4 x u64 Montgomery limbs); an fk_poseidon is host memory only.
+    pub fn fk_poseidon_params_new(t: u32, f: u32, p: u32, salt: *const c_char, out: *mut *mut fk_poseidon) -> c_int;
+    pub fn fk_poseidon_params_load(t: u32, f: u32, p: u32, c: *const u64, m: *const u64, out: *mut *mut fk_poseidon) -> c_int;
+    pub fn fk_poseidon_params_get(params: *const fk_poseidon, dims: *mut u32, c: *mut u64, m: *mut u64) -> c_int;
+    pub fn fk_poseidon_free(params: *mut fk_poseidon);
+    pub fn fk_poseidon_hash_batch(ctx: *mut fk_ctx, params: *const fk_poseidon, inputs: *const u64, n_inputs: u32, n: usize, out: *mut u64) -> c_int;
+    pub fn fk_poseidon_hash_batch_dev(ctx: *mut fk_ctx, params: *const fk_poseidon, d_inputs: *const c_void, n_inputs: u32, n: usize, d_out: *mut c_void) -> c_int;
+    pub fn fk_poseidon_sponge_batch(ctx: *mut fk_ctx, params: *const fk_poseidon, inputs: *const u64, len: u64, n: usize, out: *mut u64) -> c_int;
+    pub fn fk_poseidon_merkle_tree_dev(ctx: *mut fk_ctx, params: *const fk_poseidon, d_leaves: *const c_void, n_leaves: u64, d_nodes: *mut c_void) -> c_int;
+    pub fn fk_poseidon_merkle_root(ctx: *mut fk_ctx, params: *const fk_poseidon, leaves: *const u64, n_leaves: u64, out_root: *mut u64) -> c_int;
+    pub fn fk_poseidon_merkle_proofs_dev(ctx: *mut fk_ctx, d_nodes: *const c_void, depth: u32, d_indices: *const c_void, n: usize, d_siblings: *mut c_void) -> c_int;
+    pub fn fk_poseidon_merkle_proof_roots(ctx: *mut fk_ctx, params: *const fk_poseidon, leaves: *const u64, siblings: *const u64, indices: *const u64,
+                                          depth: u32, n: usize, out: *mut u64) -> c_int;
+    pub fn fk_poseidon_merkle_proof_roots_dev(ctx: *mut fk_ctx, params: *const fk_poseidon, d_leaves: *const c_void, d_siblings: *const c_void,
+                                              d_indices: *const c_void, depth: u32, n: usize, d_out: *mut c_void) -> c_int;
 }
