@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     FkError, Context, MultiContext, Parameters, Proof, VK, G1Point, G2Point, R1cs, prove, prove_with_rs, lib_path, load_library,
     FK_MSM_RESULT_BYTES, FK_PROOF_BYTES, EXPORTED_SYMBOLS, build_library,
     verify, verify_batch, vk_to_borsh, synthesize, sample_fr, PoseidonParams, MerkleTree,
+    jubjub_params, eddsa_hash_r, FS_MODULUS,
 )
 from . import parallel  # noqa: F401
 from . import params_io  # noqa: F401

@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     'fk_poseidon_hash_batch', 'fk_poseidon_hash_batch_dev', 'fk_poseidon_sponge_batch',
     'fk_poseidon_merkle_tree_dev', 'fk_poseidon_merkle_root', 'fk_poseidon_merkle_proofs_dev',
     'fk_poseidon_merkle_proof_roots', 'fk_poseidon_merkle_proof_roots_dev',
+    'fk_jubjub_params', 'fk_jubjub_mul_batch', 'fk_jubjub_decompress_batch',
+    'fk_eddsa_hash_r', 'fk_eddsa_sign_batch', 'fk_eddsa_verify_batch', 'fk_eddsa_verify_batch_dev',
 ]
 
 _ERR = {1: 'FK_ERR_BAD_ARG', 2: 'FK_ERR_DOMAIN_TOO_LARGE (bellman: PolynomialDegreeTooLarge)',
@@ -767,6 +769,56 @@ class PoseidonParams:
             pass
 
 
+FS_MODULUS = 2736030358979909402780800718157159386076813972158567259200215660948447373041      # the JubJub scalar field (251 bits)
+
+
+def _u256_rows(values, n=None):
+    """(n, 4) u64 canonical little-endian limbs (Fs elements, scalars) from a uint64 array or from ints below 2^256"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64:
+        a = np.ascontiguousarray(values).reshape(-1, 4)
+    else:
+        flat = np.asarray(values, dtype=object).reshape(-1)
+        a = np.zeros((len(flat), 4), np.uint64)
+        for i, v in enumerate(flat):
+            v = int(v)
+            if not 0 <= v < 1 << 256:
+                raise ValueError('not a 256-bit integer: %d' % v)
+            a[i] = int_to_limbs(v)
+    if n is not None and a.shape[0] != n:
+        raise ValueError('expected %d integers, got %d' % (n, a.shape[0]))
+    return a
+
+
+def _u256_ints(limbs):
+    return [limbs_to_int(row) for row in np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)]
+
+
+def _is_limbs(v):
+    return isinstance(v, np.ndarray) and v.dtype == np.uint64
+
+
+def jubjub_params():
+    """JubJubBN256 (engines/bn256/mod.rs:48-75) as the library derived it on the host: dict(d, g=(x, y), fs), canonical ints"""
+    lib = load_library()
+    d, g, fs = np.zeros(4, np.uint64), np.zeros(8, np.uint64), np.zeros(4, np.uint64)
+    rc = lib.fk_jubjub_params(_vp(d), _vp(g), _vp(fs))
+    if rc != 0:
+        raise FkError(rc, (lib.fk_last_error(None) or b'').decode())
+    gx, gy = _fr_ints(g)
+    return dict(d=_fr_ints(d)[0], g=(gx, gy), fs=limbs_to_int(fs))
+
+
+def eddsa_hash_r(sk, m):
+    """eddsaposeidon.rs:13-29: the nonce of a signature, Blake2s-256("__fawkes"; sk | m) mod Fs.  sk: a 256-bit int (or 4 canonical limbs);
+    m: a canonical int (or 4 Montgomery limbs).  Ints in give an int, limbs give limbs.  Host only."""
+    lib = load_library()
+    ka, ma, out = _u256_rows(sk, 1), _fr_rows(m, 1), np.zeros(4, np.uint64)
+    rc = lib.fk_eddsa_hash_r(_vp(ka), _vp(ma), _vp(out))
+    if rc != 0:
+        raise FkError(rc, (lib.fk_last_error(None) or b'').decode())
+    return out if _is_limbs(sk) and _is_limbs(m) else limbs_to_int(out)
+
+
 class MerkleTree:
     """A Poseidon Merkle tree resident in device memory (Context.merkle_tree): 2^(depth + 1) - 1 nodes, the leaves (zero-padded to
     2^depth) first, the root last."""
@@ -1346,6 +1398,58 @@ class Context:
     def merkle_proof_roots_dev(self, params, d_leaves, d_siblings, d_indices, depth, n, d_out):
         self._ck(self.lib.fk_poseidon_merkle_proof_roots_dev(self.handle, params.handle, C.c_void_p(d_leaves), C.c_void_p(d_siblings), C.c_void_p(d_indices),
                                                              C.c_uint32(depth), C.c_size_t(n), C.c_void_p(d_out)))
+
+    # ---- JubJub / EdDSA-Poseidon (native/ecc.rs, native/eddsaposeidon.rs).  Fr elements: canonical ints or Montgomery limb arrays; Fs
+    # elements (scalars, s, sk, rho): ints or canonical limb arrays.  Ints in give ints out, limb arrays in give limb arrays out.
+    def jubjub_mul(self, points, scalars):
+        """[scalars[i]] points[i] as affine (x, y); points None: the generator.  points: n pairs of ints or an (n, 2, 4) limb array"""
+        as_limbs = _is_limbs(scalars)
+        ka = _u256_rows(scalars)
+        n = ka.shape[0]
+        pa = None if points is None else _fr_rows(points if _is_limbs(points) else [c for pt in points for c in pt], 2 * n)
+        out = np.zeros((n, 2, 4), np.uint64)
+        self._ck(self.lib.fk_jubjub_mul_batch(self.handle, _vp(pa), _vp(ka), C.c_size_t(n), _vp(out)))
+        if as_limbs:
+            return out
+        v = _fr_ints(out)
+        return [(v[2 * i], v[2 * i + 1]) for i in range(n)]
+
+    def jubjub_decompress(self, xs):
+        """subgroup_decompress(x) for every x: a list of y or None (limb arrays in: (y limbs, ok flags))"""
+        as_limbs = _is_limbs(xs)
+        xa = _fr_rows(xs)
+        n = xa.shape[0]
+        y, ok = np.zeros((n, 4), np.uint64), np.zeros(n, np.uint8)
+        self._ck(self.lib.fk_jubjub_decompress_batch(self.handle, _vp(xa), C.c_size_t(n), _vp(y), _vp(ok)))
+        if as_limbs:
+            return y, ok
+        return [v if f else None for v, f in zip(_fr_ints(y), ok)]
+
+    def eddsa_sign(self, params, sks, ms, rhos=None):
+        """eddsaposeidon_sign for every (sk, m), nonce rhos[i] or (None) eddsa_hash_r(sk, m) -> (s, r_x, a_x) lists"""
+        as_limbs = _is_limbs(sks) and _is_limbs(ms)
+        ka = _u256_rows(sks)
+        n = ka.shape[0]
+        ma = _fr_rows(ms, n)
+        ra = None if rhos is None else _u256_rows(rhos, n)
+        s, r_x, a_x = (np.zeros((n, 4), np.uint64) for _ in range(3))
+        self._ck(self.lib.fk_eddsa_sign_batch(self.handle, params.handle, _vp(ka), _vp(ma), _vp(ra), C.c_size_t(n), _vp(s), _vp(r_x), _vp(a_x)))
+        if as_limbs:
+            return s, r_x, a_x
+        return _u256_ints(s), _fr_ints(r_x), _fr_ints(a_x)
+
+    def eddsa_verify(self, params, s, r, a, m):
+        """eddsaposeidon_verify for every row -> list of bool.  A row may be given out of range only as limbs (it is then rejected)"""
+        sa = _u256_rows(s)
+        n = sa.shape[0]
+        ra, aa, ma = _fr_rows(r, n), _fr_rows(a, n), _fr_rows(m, n)
+        acc = np.zeros(n, np.uint8)
+        self._ck(self.lib.fk_eddsa_verify_batch(self.handle, params.handle, _vp(sa), _vp(ra), _vp(aa), _vp(ma), C.c_size_t(n), _vp(acc)))
+        return [bool(v) for v in acc]
+
+    def eddsa_verify_dev(self, params, d_s, d_r, d_a, d_m, n, d_accept):
+        self._ck(self.lib.fk_eddsa_verify_batch_dev(self.handle, params.handle, C.c_void_p(d_s), C.c_void_p(d_r), C.c_void_p(d_a), C.c_void_p(d_m),
+                                                    C.c_size_t(n), C.c_void_p(d_accept)))
 
 
 class _MultiHandle:

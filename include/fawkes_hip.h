@@ -597,6 +597,36 @@ int fk_poseidon_merkle_proof_roots(fk_ctx *ctx, const fk_poseidon *params, const
 int fk_poseidon_merkle_proof_roots_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_leaves, const void *d_siblings,
                                        const void *d_indices, uint32_t depth, size_t n, void *d_out);
 
+/* ---------------------------------------------------------------- JubJub and EdDSA-Poseidon on the device
+ * native/ecc.rs and native/eddsaposeidon.rs next to the prover: JubJubBN256 (-x^2 + y^2 = 1 + d x^2 y^2 over Fr, d = -168696/168700),
+ * EdwardsPoint::mul, subgroup_decompress, eddsaposeidon_sign / eddsaposeidon_verify, one item per GPU lane.  Two conventions:
+ *   Fr elements (r, a, m, r_x, a_x, point coordinates, d) are Montgomery LE limbs, 4 x u64, like everywhere in this header;
+ *   Fs elements (s, sk, rho, scalars, fs) are CANONICAL little-endian 4 x u64 integers: what Num<Fs>::to_uint() and Borsh give.
+ * Fs = 2736030358979909402780800718157159386076813972158567259200215660948447373041 (251 bits).  A point is x | y, 8 x u64.
+ * The hash of a signature is poseidon([r, a, m]) with t = 4 parameters; any other t is FK_ERR_BAD_ARG.  n == 0 is a no-op.
+ *   fk_jubjub_params          host only.  d; the generator g.x | g.y, derived by the library as the reference does (from_scalar_raw of the
+ *                             seedbox "edwards_g", times the cofactor); fs.  Any pointer may be NULL.
+ *   fk_jubjub_mul_batch       out[i] = [scalars[i]] points[i], affine; points == NULL: the generator.  A scalar is any 256-bit integer.
+ *                             A coordinate image >= r is FK_ERR_BAD_ARG.  The points are taken to be on the curve.
+ *   fk_jubjub_decompress_batch  subgroup_decompress(x[i]): ok[i] = 1 and y[i], or ok[i] = 0 and a zero y row.  An x image >= r is FK_ERR_BAD_ARG.
+ *   fk_eddsa_hash_r           host only.  The reference's nonce: Blake2s-256, personalisation "__fawkes", over the 32 little-endian bytes of sk and
+ *                             of the canonical value of m; the digest read as a little-endian integer, mod Fs.
+ *   fk_eddsa_sign_batch       (s, r_x, a_x) of eddsaposeidon_sign(sk, m) with the nonce rho[i], or fk_eddsa_hash_r(sk[i], m[i]) where rho == NULL.
+ *                             r_x and a_x may be NULL.  sk or rho >= Fs, or an m image >= r, is FK_ERR_BAD_ARG.
+ *   fk_eddsa_verify_batch     accept[i] = eddsaposeidon_verify(s[i], r[i], a[i], m[i]).  A row whose s is >= Fs, or whose r / a / m image is >= r,
+ *                             is rejected (0) and the call still returns FK_OK: the reference's types cannot hold such values.
+ *   fk_eddsa_verify_batch_dev the same on device arrays (d_s .. d_m n x 32 bytes, d_accept n bytes); asynchronous on the library's stream. */
+int fk_jubjub_params(uint64_t d[4], uint64_t g[8], uint64_t fs[4]);
+int fk_jubjub_mul_batch(fk_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t n, uint64_t *out);
+int fk_jubjub_decompress_batch(fk_ctx *ctx, const uint64_t *x, size_t n, uint64_t *y, uint8_t *ok);
+int fk_eddsa_hash_r(const uint64_t sk[4], const uint64_t m[4], uint64_t rho[4]);
+int fk_eddsa_sign_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *sk, const uint64_t *m, const uint64_t *rho, size_t n,
+                        uint64_t *s, uint64_t *r_x, uint64_t *a_x);
+int fk_eddsa_verify_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *s, const uint64_t *r, const uint64_t *a, const uint64_t *m,
+                          size_t n, uint8_t *accept);
+int fk_eddsa_verify_batch_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_s, const void *d_r, const void *d_a, const void *d_m,
+                              size_t n, void *d_accept);
+
 /* Kernel timing measured with HIP events on the library's stream since the last reset, summed over
  * launches.  which: 0 = msm_accumulate_kernel<Fq> (G1 bucket accumulation; units = points per launch),
  * 1 = msm_accumulate_kernel<Fq2> (G2), 2 = ntt_pass_kernel (units = elements per pass); 3 / 4 = the same kernels as 0 / 1

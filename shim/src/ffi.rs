@@ -95,4 +95,17 @@ extern "C" {
                                           depth: u32, n: usize, out: *mut u64) -> c_int;
     pub fn fk_poseidon_merkle_proof_roots_dev(ctx: *mut fk_ctx, params: *const fk_poseidon, d_leaves: *const c_void, d_siblings: *const c_void,
                                               d_indices: *const c_void, depth: u32, n: usize, d_out: *mut c_void) -> c_int;
+
+    // JubJub and EdDSA-Poseidon on the device (native/ecc.rs, native/eddsaposeidon.rs).  Fr elements (r, a, m, coordinates) are `Num<Fr>`
+    // images; Fs elements (s, sk, rho, scalars) are canonical little-endian 4 x u64 integers (`Num<Fs>::to_uint()`).
+    pub fn fk_jubjub_params(d: *mut u64, g: *mut u64, fs: *mut u64) -> c_int;
+    pub fn fk_jubjub_mul_batch(ctx: *mut fk_ctx, points: *const u64, scalars: *const u64, n: usize, out: *mut u64) -> c_int;
+    pub fn fk_jubjub_decompress_batch(ctx: *mut fk_ctx, x: *const u64, n: usize, y: *mut u64, ok: *mut u8) -> c_int;
+    pub fn fk_eddsa_hash_r(sk: *const u64, m: *const u64, rho: *mut u64) -> c_int;
+    pub fn fk_eddsa_sign_batch(ctx: *mut fk_ctx, params: *const fk_poseidon, sk: *const u64, m: *const u64, rho: *const u64, n: usize,
+                               s: *mut u64, r_x: *mut u64, a_x: *mut u64) -> c_int;
+    pub fn fk_eddsa_verify_batch(ctx: *mut fk_ctx, params: *const fk_poseidon, s: *const u64, r: *const u64, a: *const u64, m: *const u64,
+                                 n: usize, accept: *mut u8) -> c_int;
+    pub fn fk_eddsa_verify_batch_dev(ctx: *mut fk_ctx, params: *const fk_poseidon, d_s: *const c_void, d_r: *const c_void, d_a: *const c_void,
+                                     d_m: *const c_void, n: usize, d_accept: *mut c_void) -> c_int;
 }
