@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     'fk_prove_assemble',
     'fk_fr_mul_batch', 'fk_ntt', 'fk_ntt_dev', 'fk_quotient_h', 'fk_quotient_h_dev',
     'fk_msm_g1', 'fk_msm_g2', 'fk_msm_g1_dev', 'fk_msm_g2_dev',
-    'fk_gen_points_g1_dev', 'fk_gen_points_g2_dev', 'fk_gen_scalars_dev',
+    'fk_gen_points_g1_dev', 'fk_gen_points_g2_dev', 'fk_gen_scalars_dev', 'fk_msm_plan', 'fk_msm_front_dump',
     'fk_synthesize', 'fk_roctx_active', 'fk_stats_reset', 'fk_stats_get', 'fk_calibrate', 'fk_verify', 'fk_verify_batch_dev', 'fk_shard_range', 'fk_h_shard_range', 'fk_work_shard_ranges', 'fk_work_shard_ranges_q0',
     'fk_dq_gather_dev', 'fk_dq_local_dev', 'fk_dq_cross_dev', 'fk_dq_cross_sub_dev',
     'fk_setup', 'fk_setup_tiled', 'fk_r1cs_load_tiled', 'fk_key_download', 'fk_key_load_bellman', 'fk_key_write_bellman', 'fk_key_vk', 'fk_key_counts', 'fk_key_precomputed', 'fk_key_load_profile', 'fk_key_levels_plan', 'fk_key_derive_levels', 'fk_key_levels_headroom', 'fk_key_drop_levels',
@@ -103,6 +103,18 @@ class R1csStruct(C.Structure):
                 ('a_ptr', C.c_void_p), ('a_col', C.c_void_p), ('a_val', C.c_void_p),
                 ('b_ptr', C.c_void_p), ('b_col', C.c_void_p), ('b_val', C.c_void_p),
                 ('c_ptr', C.c_void_p), ('c_col', C.c_void_p), ('c_val', C.c_void_p)]
+
+
+class MsmPlanInfo(C.Structure):
+    """fk_msm_plan_info: the window plan of one multiplication and the compile-time limits it is sized against"""
+    _fields_ = [('n', C.c_uint64), ('chunk', C.c_uint64)] + [(f, C.c_uint32) for f in (
+        'c', 'W', 'B', 'cb', 'wide', 'nchunks', 'cap', 'L', 'T', 'nblk', 'LB', 'nhi', 'nlo',
+        's1_tile', 's2_tile', 's2_max_hi', 'over_max', 'seg_min', 'seg_max', 'size_bins')]
+
+
+class MsmDynInfo(C.Structure):
+    """fk_msm_dyn_info: what the front of a multiplication decided on the device"""
+    _fields_ = [(f, C.c_uint32) for f in ('cap', 'n_over', 'seg', 'n_tasks', 'n_obs', 'error')] + [('adds', C.c_uint64)]
 
 
 def load_library():
@@ -875,6 +887,7 @@ class MerkleTree:
 
 class Context:
     """One GPU (one process per GPU for multi-GPU runs).  Raises FkError if no GPU is usable."""
+    _window_bits = 0          # what set_window_bits last asked for (msm_front_dump sizes its buffers from it)
 
     def __init__(self, device_id=0, _borrowed=None):
         self.lib = load_library()
@@ -1000,6 +1013,7 @@ class Context:
 
     def set_window_bits(self, c):
         self._ck(self.lib.fk_set_window_bits(self.handle, C.c_uint(c)))
+        self._window_bits = c
 
     # ---- keys
     def load_key(self, params, shard_index=0, shard_count=1, z_frac=Z_EQUAL_SPLIT):
@@ -1085,6 +1099,42 @@ class Context:
     def msm_g2_dev(self, d_bases, d_scalars, n):
         out = np.zeros(128, np.uint8)
         self._ck(self.lib.fk_msm_g2_dev(self.handle, C.c_void_p(d_bases), C.c_void_p(d_scalars), C.c_size_t(n), _vp(out)))
+        return out
+
+    # ---- inspection of the multiplication's front (tests)
+    @staticmethod
+    def msm_plan(n, window_bits=0, merged=False):
+        return msm_plan(n, window_bits, merged)
+
+    def msm_front_dump(self, scalars, merged=False):
+        """fk_msm_front_dump over host scalars ((n, 4) uint64 Montgomery limbs): the plan (under the context's window bits) and every table
+        the front of the multiplication left, as numpy arrays -- digits, sorted (W, n), totals, starts (W, B), perm (W * B; merged: B, and
+        mt: the B merged bucket lengths), dyn (dict), tasks (n_tasks, 2: bucket, segment), obs (n_obs, 3: bucket, first task, tasks)."""
+        scalars = _fr(scalars)
+        n = scalars.shape[0]
+        self.set_window_bits(self._window_bits)      # the buffers below are sized from these bits: the library must not hold others
+        p = msm_plan(n, self._window_bits, merged)
+        W, B = p['W'], p['B']
+        out = dict(plan=p, digits=np.zeros((W, n), np.uint32), sorted=np.zeros((W, n), np.uint32), totals=np.zeros((W, B), np.uint32),
+                   starts=np.zeros((W, B), np.uint32))
+        perm = np.zeros(2 * B if merged else W * B, np.uint32)
+        # every segment holds at least seg_min entries but the last one of its bucket, and at most over_max buckets are tabled
+        tasks_cap, obs_cap = W * n // p['seg_min'] + p['over_max'] + 1, p['over_max']
+        tasks, obs, dyn = np.zeros((tasks_cap, 2), np.uint32), np.zeros((obs_cap, 3), np.uint32), MsmDynInfo()
+        d_s = self.dev_alloc(max(n, 1) * 32)
+        try:
+            if n:
+                self.upload(d_s, scalars)
+            self._ck(self.lib.fk_msm_front_dump(self.handle, C.c_void_p(d_s), C.c_size_t(n), C.c_int(int(merged)), _vp(out['digits']), _vp(out['sorted']),
+                                                _vp(out['totals']), _vp(out['starts']), _vp(perm), C.byref(dyn), _vp(tasks), C.c_size_t(tasks_cap),
+                                                _vp(obs), C.c_size_t(obs_cap)))
+        finally:
+            self.dev_free(d_s)
+        out['dyn'] = {f: int(getattr(dyn, f)) for f, _ in MsmDynInfo._fields_}
+        if out['dyn']['n_tasks'] > tasks_cap or out['dyn']['n_obs'] > obs_cap:
+            raise FkError(4, 'msm front dump: %d tasks, %d fold groups exceed the bounds %d, %d' % (out['dyn']['n_tasks'], out['dyn']['n_obs'], tasks_cap, obs_cap))
+        out['perm'], out['mt'] = (perm[:B], perm[B:]) if merged else (perm, None)
+        out['tasks'], out['obs'] = tasks[:out['dyn']['n_tasks']], obs[:out['dyn']['n_obs']]
         return out
 
     def gen_points_g1_dev(self, dptr, n, seed):
@@ -1670,6 +1720,15 @@ def assemble(key_handle, parts, r, s, ctx=None):
         msg = lib.fk_last_error(ctx.handle) if ctx else b''
         raise FkError(rc, msg.decode() if msg else '')
     return out
+
+
+def msm_plan(n, window_bits=0, merged=False):
+    """fk_msm_plan (host only, no GPU): dict of the window plan for n points and of the limits it is sized against"""
+    info = MsmPlanInfo()
+    rc = load_library().fk_msm_plan(C.c_size_t(n), C.c_uint(window_bits), C.c_int(int(merged)), C.byref(info))
+    if rc != 0:
+        raise FkError(rc, 'fk_msm_plan')
+    return {f: int(getattr(info, f)) for f, _ in MsmPlanInfo._fields_}
 
 
 def shard_range(n, index, count):

@@ -1219,6 +1219,16 @@ static int queue_tail(MsmJob<F> j) {
     return FK_OK;
 }
 
+// Lane `li` has been taken: the next multiplication goes to the lane after it.
+static void lanes_advance(fk_ctx *ctx, int li) {
+    // FK_MSM_LANES (experiment builds): fewer lanes -- never while pieces are deferred (sorts-first schedule): its deferred
+    // accumulations and tails hold pointers into their lane's buffers, so every multiplication needs a lane of its own there
+    static const int t_lanes = tune("FK_MSM_LANES", 0);
+    const int n_lanes = (t_lanes >= 1 && t_lanes <= MSM_LANES && !ctx->defer_back && ctx->deferred.empty())
+                            ? t_lanes : (ctx->lanes_in_use >= 2 && ctx->lanes_in_use <= MSM_LANES ? ctx->lanes_in_use : MSM_LANES);
+    ctx->lane_prev = li; ctx->lane_next = (li + 1) % n_lanes;
+}
+
 // Queues one multiplication on a lane: digits, two-pass bucket sort, size ordering, accumulation, oversized buckets, bucket
 // reduction and the download of the window sums (with the addition count and the device-side error word behind them) -- all
 // without the host waiting anywhere (the only synchronisation left is when a lane's scratch buffers have to GROW, i.e. in
@@ -1248,12 +1258,7 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
     const int li = have_sort ? ctx->lane_prev : ctx->lane_next;
     MsmLane &ln = ctx->lanes[li];
     if (!ln.st) FK_SET_ERR(ctx, FK_ERR_HIP, "msm: the context's streams were not created");      // (streams_init: fk_init, fk_trim)
-    // FK_MSM_LANES (experiment builds): fewer lanes -- never while pieces are deferred (sorts-first schedule): its deferred
-    // accumulations and tails hold pointers into their lane's buffers, so every multiplication needs a lane of its own there
-    static const int t_lanes = tune("FK_MSM_LANES", 0);
-    const int n_lanes = (t_lanes >= 1 && t_lanes <= MSM_LANES && !ctx->defer_back && ctx->deferred.empty())
-                            ? t_lanes : (ctx->lanes_in_use >= 2 && ctx->lanes_in_use <= MSM_LANES ? ctx->lanes_in_use : MSM_LANES);
-    ctx->lane_prev = li; ctx->lane_next = (li + 1) % n_lanes;
+    lanes_advance(ctx, li);
     if (ready) FK_HIP(ctx, hipStreamWaitEvent(ln.st, ready, 0));      // (the front of the multiplication runs on the lane's stream as well)
     else {
         FK_HIP(ctx, hipEventRecord(ln.ev_in, ctx->stream));        // scalars / bases produced on the main stream
@@ -1386,6 +1391,58 @@ int msm_g1_dev(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t
 }
 int msm_g2_dev(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, G2Xyzz *out, bool reuse_sort, const KeyPre *pre) {
     return msm_run<Fq2>(ctx, d_bases, d_scalars, n, out, reuse_sort, pre);
+}
+
+// ------------------------------------------------------------------------------------------ inspection entry points (tests)
+// fk_msm_plan: the window plan of a multiplication of n points and the compile-time limits it is sized against.  Host only.
+static void msm_plan_info(size_t n, unsigned window_bits, bool merged, fk_msm_plan_info *out) {
+    const MsmPlan p = make_plan(n, window_bits, merged);
+    *out = fk_msm_plan_info{(uint64_t)p.n, (uint64_t)p.chunk, p.c, p.W, p.B, p.cb, p.wide, p.nchunks, p.cap, p.L, p.T, p.nblk, p.LB, p.nhi, p.nlo,
+                            S1_TILE, S2_TILE, S2_MAX_HI, OVER_MAX, SEG_MIN, SEG_MAX, SIZE_BINS};
+}
+
+// fk_msm_front_dump: the front of a multiplication (msm_reserve, queue_sort, queue_size_order -- what msm_begin queues before the
+// accumulation) on the next lane in turn, then every table it left, copied to the caller's host buffers.  The front never reads
+// the bases, so the job carries none.  An idle tail record lends msm_reserve its buffers and is not claimed; the lane forgets the
+// sort, so that a later reuse_sort multiplication cannot adopt it.
+static int msm_front_dump(fk_ctx *ctx, const Fr *d_scalars, size_t n, bool merged, uint32_t *digits, uint32_t *sorted, uint32_t *totals, uint32_t *starts,
+                          uint32_t *perm, fk_msm_dyn_info *dyn_out, uint32_t *tasks, size_t tasks_cap, uint32_t *obs, size_t obs_cap) {
+    if (n == 0) return FK_OK;
+    if (n >= ((size_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: n too large");
+    if (ctx->defer_back || !ctx->deferred.empty() || !ctx->deferred_tails.empty() || ctx->wit_active || ctx->early.done)
+        FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm front dump: a proof is in flight on this context");
+    int ti = -1;
+    for (int i = 0; i < MSM_TAILS; i++) if (!ctx->tails[i].active) { ti = i; break; }
+    if (ti < 0) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: too many outstanding multiplications");
+    const int li = ctx->lane_next;
+    MsmLane &ln = ctx->lanes[li];
+    if (!ln.st) FK_SET_ERR(ctx, FK_ERR_HIP, "msm: the context's streams were not created");
+    lanes_advance(ctx, li);
+    FK_HIP(ctx, hipEventRecord(ln.ev_in, ctx->stream));        // scalars produced on the main stream
+    FK_HIP(ctx, hipStreamWaitEvent(ln.st, ln.ev_in, 0));
+    MsmJob<Fq> job{};
+    job.ctx = ctx; job.p = make_plan(n, ctx->window_bits, merged); job.ln = &ln; job.tl = &ctx->tails[ti];
+    job.scalars = d_scalars; job.n = n; job.merged = merged;
+    const MsmPlan &p = job.p;
+    FK_TRY(msm_reserve(job));
+    FK_TRY(queue_sort(job));
+    FK_TRY(queue_size_order(job));
+    ln.last_sort_scalars = nullptr;
+    FK_HIP(ctx, hipStreamSynchronize(ln.st));
+    const size_t Wn = (size_t)p.W * n, WB = job.WB;
+    FK_HIP(ctx, hipMemcpy(digits, job.digits, Wn * 4, hipMemcpyDeviceToHost));
+    FK_HIP(ctx, hipMemcpy(sorted, job.sorted, Wn * 4, hipMemcpyDeviceToHost));
+    FK_HIP(ctx, hipMemcpy(totals, job.totals, WB * 4, hipMemcpyDeviceToHost));
+    FK_HIP(ctx, hipMemcpy(starts, job.starts, WB * 4, hipMemcpyDeviceToHost));
+    FK_HIP(ctx, hipMemcpy(perm, job.perm, (merged ? 2 * (size_t)p.B : WB) * 4, hipMemcpyDeviceToHost));      // merged: perm[B], then the merged lengths mt[B]
+    MsmDyn h{};
+    FK_HIP(ctx, hipMemcpy(&h, job.dyn, sizeof h, hipMemcpyDeviceToHost));
+    *dyn_out = fk_msm_dyn_info{h.cap, h.n_over, h.seg, h.n_tasks, h.n_obs, h.error, (uint64_t)h.adds};
+    static_assert(sizeof(Task) == 8 && sizeof(OverBucket) == 12, "fk_msm_front_dump hands these out as 2 and 3 words");
+    const size_t nt = std::min<size_t>(std::min<size_t>(h.n_tasks, job.max_tasks), tasks_cap), no = std::min<size_t>(std::min<size_t>(h.n_obs, OVER_MAX), obs_cap);
+    if (nt) FK_HIP(ctx, hipMemcpy(tasks, job.tasks, nt * sizeof(Task), hipMemcpyDeviceToHost));
+    if (no) FK_HIP(ctx, hipMemcpy(obs, job.obs, no * sizeof(OverBucket), hipMemcpyDeviceToHost));
+    return FK_OK;
 }
 
 // ------------------------------------------------------------------------------------------ fixed-base precomputation of a key
@@ -1731,3 +1788,18 @@ int compact_scalars(fk_ctx *ctx, const Fr *d_z, const uint8_t *d_density, size_t
 }
 
 }  // namespace fk
+
+// ------------------------------------------------------------------------------------------ C ABI of the inspection entry points
+int fk_msm_plan(size_t n, unsigned window_bits, int merged, fk_msm_plan_info *out) {
+    if (!out) return FK_ERR_BAD_ARG;
+    fk::msm_plan_info(n, window_bits, merged != 0, out);
+    return FK_OK;
+}
+
+int fk_msm_front_dump(fk_ctx *ctx, const void *d_scalars, size_t n, int merged, uint32_t *digits, uint32_t *sorted, uint32_t *totals, uint32_t *starts,
+                      uint32_t *perm, fk_msm_dyn_info *dyn, uint32_t *tasks, size_t tasks_cap, uint32_t *obs, size_t obs_cap) { return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    if (n && (!d_scalars || !digits || !sorted || !totals || !starts || !perm || !dyn || (!tasks && tasks_cap) || (!obs && obs_cap))) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_HIP(ctx, hipSetDevice(ctx->device));
+    return fk::msm_front_dump(ctx, (const fk::Fr *)d_scalars, n, merged != 0, digits, sorted, totals, starts, perm, dyn, tasks, tasks_cap, obs, obs_cap);
+}); }

@@ -302,6 +302,32 @@ int fk_gen_points_g2_dev(fk_ctx *ctx, void *d_out, size_t n, uint64_t seed);
 /* n pseudo-random Montgomery Fr elements; kind 0 = uniform, 1 = witness-like (half in {0,1}), 2 = the benchmark witness's mix (5.3 % zeros,
  * 2.5 % ones, the rest dense and pairwise distinct) */
 int fk_gen_scalars_dev(fk_ctx *ctx, void *d_out, size_t n, uint64_t seed, int kind);
+/* Inspection entry points of the multiplication's front (tests; on no proving path).
+ * fk_msm_plan: host only, no context and no GPU -- the window plan the library makes for n points under window_bits (as fk_set_window_bits;
+ * 0 = the library's choice), merged != 0: the plan of the form with precomputed levels.  Windows: the first `wide` of the W windows have
+ * cb + 1 bits, the others cb (255 in all); c = cb + 1; B = 2^(c-1) buckets per window, B = nhi * nlo (bins of the two sort passes, nlo = 2^LB);
+ * chunk / nchunks: the first sort pass's split of n; cap: the planned entries a bucket-lane walks itself; L, T, nblk: buckets per lane,
+ * lanes and workgroups per window of the bucket reduction.  The s1_tile .. size_bins fields are the compile-time limits the plan is sized against. */
+typedef struct {
+    uint64_t n, chunk;
+    uint32_t c, W, B, cb, wide, nchunks, cap, L, T, nblk, LB, nhi, nlo;
+    uint32_t s1_tile, s2_tile, s2_max_hi, over_max, seg_min, seg_max, size_bins;
+} fk_msm_plan_info;
+int fk_msm_plan(size_t n, unsigned window_bits, int merged, fk_msm_plan_info *out);
+/* what the front decides on the device: the final cap, the buckets above it, the segment length and the segment tasks / fold groups
+ * of those buckets, the error word (0 = fine) and the mixed additions the accumulation will do */
+typedef struct {
+    uint32_t cap, n_over, seg, n_tasks, n_obs, error;
+    uint64_t adds;
+} fk_msm_dyn_info;
+/* fk_msm_front_dump: runs the front of one multiplication over n device-resident Montgomery scalars -- digits, two-pass bucket sort, oversized
+ * buckets, size order, exactly what a multiplication queues before its accumulation, under the context's window bits -- waits for it and
+ * copies its tables to host buffers: digits and sorted (W * n words, window-major; bit 31 = the digit's sign), totals and starts (W * B
+ * words), perm (W * B words; merged: B words of perm followed by the B merged bucket lengths), the device-side record, and the first
+ * n_tasks (2 words each: bucket, segment) and n_obs (3 words each: bucket, first task, tasks) table entries, at most tasks_cap / obs_cap
+ * of them.  Uses a lane like a multiplication and leaves nothing outstanding.  n == 0: nothing is written. */
+int fk_msm_front_dump(fk_ctx *ctx, const void *d_scalars, size_t n, int merged, uint32_t *digits, uint32_t *sorted, uint32_t *totals, uint32_t *starts,
+                      uint32_t *perm, fk_msm_dyn_info *dyn, uint32_t *tasks, size_t tasks_cap, uint32_t *obs, size_t obs_cap);
 
 /* ---------------------------------------------------------------- synthesis (host side of the boundary)
  * ProvingAssignment::enforce/eval restated (App. A.1): evaluates a CSR R1CS on the assignment and

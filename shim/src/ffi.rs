@@ -1,6 +1,6 @@
 //! `extern "C"` mirror of include/fawkes_hip.h -- only the entry points the shim uses.
 //! Layouts are `#[repr(C)]` images of the C structs; every function returns FK_OK (0) or an error code.
-#![allow(non_camel_case_types, dead_code)]
+#![allow(non_camel_case_types, non_snake_case, dead_code)]
 use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)] pub struct fk_ctx { _p: [u8; 0] }
@@ -30,6 +30,21 @@ pub struct fk_key_desc {
     pub b_g1: *const u8, pub b_g2: *const u8, pub n_b: u64,
     pub shard_index: u32, pub shard_count: u32,
     pub z_frac_lo: f64, pub z_frac_hi: f64,
+}
+
+/// `fk_msm_plan_info` (fawkes_hip.h): the window plan of one multiplication and the compile-time limits it is sized against (inspection).
+#[repr(C)]
+pub struct fk_msm_plan_info {
+    pub n: u64, pub chunk: u64,
+    pub c: u32, pub W: u32, pub B: u32, pub cb: u32, pub wide: u32, pub nchunks: u32, pub cap: u32,
+    pub L: u32, pub T: u32, pub nblk: u32, pub LB: u32, pub nhi: u32, pub nlo: u32,
+    pub s1_tile: u32, pub s2_tile: u32, pub s2_max_hi: u32, pub over_max: u32, pub seg_min: u32, pub seg_max: u32, pub size_bins: u32,
+}
+/// `fk_msm_dyn_info` (fawkes_hip.h): what the front of a multiplication decided on the device (inspection).
+#[repr(C)]
+pub struct fk_msm_dyn_info {
+    pub cap: u32, pub n_over: u32, pub seg: u32, pub n_tasks: u32, pub n_obs: u32, pub error: u32,
+    pub adds: u64,
 }
 
 extern "C" {
@@ -71,6 +86,12 @@ extern "C" {
     pub fn fk_multi_prove_r1cs_submit(multi: *mut fk_multi, key: *const fk_multi_key, r1cs: *const fk_multi_r1cs, z: *const u64,
                                       r: *const u64, s: *const u64, ticket: *mut c_int) -> c_int;
     pub fn fk_multi_prove_r1cs_wait(multi: *mut fk_multi, ticket: c_int, out_proof: *mut u8, timings: *mut c_void) -> c_int;
+
+    // inspection of the multiplication's front (tests): the window plan (host only) and the tables the front leaves on the device
+    pub fn fk_msm_plan(n: usize, window_bits: u32, merged: c_int, out: *mut fk_msm_plan_info) -> c_int;
+    pub fn fk_msm_front_dump(ctx: *mut fk_ctx, d_scalars: *const c_void, n: usize, merged: c_int, digits: *mut u32, sorted: *mut u32,
+                             totals: *mut u32, starts: *mut u32, perm: *mut u32, dyn_: *mut fk_msm_dyn_info, tasks: *mut u32, tasks_cap: usize,
+                             obs: *mut u32, obs_cap: usize) -> c_int;
 
     // verifier (verifier.rs:75-81): vk = fawkes' Borsh `VK`, inputs = Montgomery Fr without the leading ONE, proof = Borsh `Proof`.
     // fk_verify is host code (ctx may be null); the batch form judges `count` proofs of one key on the GPU, accept[i] = 1 / 0

@@ -171,3 +171,62 @@ def test_msm_many_repeated_scalars(ctx, oracle):
     n = sc.shape[0]
     bases = g1_bases(n, seed=9)
     assert ctx.msm_g1(bases, sc).tobytes() == oracle.msm_g1(bases, sc).tobytes()
+
+
+def _forced(ctx, c, fn, *args):
+    ctx.set_window_bits(c)
+    try:
+        return fn(*args)
+    finally:
+        ctx.set_window_bits(0)
+
+
+@pytest.fixture(scope='module')
+def boundary_inputs(oracle):
+    """32 769 G1 points, uniform scalars and the oracle's sums over the first 8193, 16 385 and 32 769 of them (computed once)"""
+    rng = np.random.default_rng(8193)
+    bases = g1_bases(32769, seed=12)
+    vals = [int.from_bytes(rng.bytes(40), 'little') % R for _ in range(32769)]
+    sc = oracle.limbs_arr([ref.to_mont(v, R) for v in vals])
+    return bases, sc, {n: oracle.msm_g1(bases[:n], sc[:n]).tobytes() for n in (8193, 16385, 32769)}
+
+
+@pytest.mark.parametrize('c', [8, 12, 14, 22])
+@pytest.mark.parametrize('n', [8193, 16385, 32769])
+def test_msm_g1_at_the_sort_boundaries(ctx, boundary_inputs, n, c):
+    """whole multiplications at the shapes tests/test_gpu_msm_front.py takes the front through: one entry past a sort tile (8192) and past
+    one and two first-pass chunks (16 384), with one high bin (c = 8), two (c = 12) and 2048 low bins (c = 22); the bucket reduction runs
+    with 1 (c = 8, 12), 2 (c = 14) and 64 (c = 22) buckets per lane"""
+    bases, sc, want = boundary_inputs
+    assert _forced(ctx, c, ctx.msm_g1, bases[:n], sc[:n]).tobytes() == want[n], (n, c)
+
+
+def _digit_edge_scalars(c):
+    """the scalar classes of tests/test_gpu_msm_front.py for c-bit windows: 0, 1, r - 1, 2^253 - 1 (a carry through every window) and,
+    per window, the raw digits 2^(cw-1) (stays positive) and 2^(cw-1) + 1 (first negative) and a single bit at its first and last position"""
+    from fawkes_crypto_amd import api
+    p = api.msm_plan(300, c)
+    out, o = [0, 1, R - 1, (1 << 253) - 1], 0
+    for w in range(p['W']):
+        cw = p['cb'] + (1 if w < p['wide'] else 0)
+        out += [v for v in ((1 << (cw - 1)) << o, ((1 << (cw - 1)) + 1) << o, 1 << o, 1 << (o + cw - 1)) if v < R]
+        o += cw
+    return out
+
+
+@pytest.mark.parametrize('c', [8, 12, 22])
+def test_msm_g1_carry_chain_and_digit_boundaries(ctx, oracle, c):
+    n = 300
+    vals = _digit_edge_scalars(c)
+    vals = (vals * (n // len(vals) + 1))[:n]
+    assert (1 << 253) - 1 in vals and R - 1 in vals
+    bases, sc = g1_bases(n, seed=13), oracle.limbs_arr([ref.to_mont(v, R) for v in vals])
+    assert _forced(ctx, c, ctx.msm_g1, bases, sc).tobytes() == oracle.msm_g1(bases, sc).tobytes(), c
+
+
+def test_msm_g2_one_entry_past_a_sort_tile(ctx, oracle):
+    n = 8193
+    rng = np.random.default_rng(81)
+    bases = g2_bases(n, seed=14)
+    sc = oracle.limbs_arr([ref.to_mont(int.from_bytes(rng.bytes(40), 'little') % R, R) for _ in range(n)])
+    assert _forced(ctx, 8, ctx.msm_g2, bases, sc).tobytes() == oracle.msm_g2(bases, sc).tobytes()
