@@ -7,13 +7,17 @@ Reference interface mirrored here (file:line under /root/reference/fawkes-crypto
   prove                 prover.rs:63-90    (returns (public inputs without ONE, proof))
   G1Point / G2Point     group.rs:13-122    ((0,0) <=> infinity)
   OsRng                 osrng.rs:12-18     (r, s source; `prove_with_rs` bypasses it)
-No oracle code is imported here, and nothing falls back to the CPU.
+No oracle code is imported here, and nothing falls back to the CPU.  The C prototypes (restype / argtypes of every fk_* function) and the
+ctypes structs live in _abi.py; load_library() applies them, so the calls below pass plain Python values.
 """
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
+
+from . import _abi
+from ._abi import KeyDesc, Timings, R1csStruct, MsmPlanInfo, MsmDynInfo  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FK_PROOF_BYTES = 256
@@ -24,35 +28,8 @@ FK_MSM_RESULT_BYTES = 4 * 64 + 128
 FR_MODULUS = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 FQ_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 
-# every symbol include/fawkes_hip.h declares (tests check the .so exports all of them)
-EXPORTED_SYMBOLS = [
-    'fk_init', 'fk_free', 'fk_trim', 'fk_last_error', 'fk_set_window_bits',
-    'fk_dev_alloc', 'fk_dev_free', 'fk_upload', 'fk_download', 'fk_dev_copy', 'fk_sync', 'fk_stream',
-    'fk_host_alloc', 'fk_host_free', 'fk_witness_upload_async', 'fk_witness_ptr', 'fk_witness_slot', 'fk_witness_upload_part_async', 'fk_witness_mark_ready', 'fk_prove_r1cs_submit', 'fk_prove_r1cs_wait',
-    'fk_key_load', 'fk_key_synthetic', 'fk_key_shard_info', 'fk_key_shard_info2', 'fk_key_host_vk', 'fk_key_free',
-    'fk_prove', 'fk_prove_dev', 'fk_prove_msms', 'fk_prove_msms_dev', 'fk_prove_msms_z_dev', 'fk_prove_msm_h_dev', 'fk_prove_msm_array_dev', 'fk_prove_msms_hz_dev',
-    'fk_prove_msms_z_begin_dev', 'fk_prove_msms_finish_dev', 'fk_prove_msms_hz_r1cs_dev', 'fk_prove_msms_z_begin_r1cs_dev',
-    'fk_prove_assemble',
-    'fk_fr_mul_batch', 'fk_ntt', 'fk_ntt_dev', 'fk_quotient_h', 'fk_quotient_h_dev',
-    'fk_msm_g1', 'fk_msm_g2', 'fk_msm_g1_dev', 'fk_msm_g2_dev',
-    'fk_gen_points_g1_dev', 'fk_gen_points_g2_dev', 'fk_gen_scalars_dev', 'fk_msm_plan', 'fk_msm_front_dump',
-    'fk_synthesize', 'fk_roctx_active', 'fk_stats_reset', 'fk_stats_get', 'fk_calibrate', 'fk_verify', 'fk_verify_batch_dev', 'fk_shard_range', 'fk_h_shard_range', 'fk_work_shard_ranges', 'fk_work_shard_ranges_q0',
-    'fk_dq_gather_dev', 'fk_dq_local_dev', 'fk_dq_cross_dev', 'fk_dq_cross_sub_dev',
-    'fk_setup', 'fk_setup_tiled', 'fk_r1cs_load_tiled', 'fk_key_download', 'fk_key_load_bellman', 'fk_key_write_bellman', 'fk_key_vk', 'fk_key_counts', 'fk_key_precomputed', 'fk_key_load_profile', 'fk_key_levels_plan', 'fk_key_derive_levels', 'fk_key_levels_headroom', 'fk_key_drop_levels',
-    'fk_gates_decode', 'fk_gates_free', 'fk_gates_info', 'fk_gates_export', 'fk_r1cs_load_gates', 'fk_gates_profile',
-    'fk_gates_encode', 'fk_blob_data', 'fk_blob_profile', 'fk_blob_free',
-    'fk_r1cs_load', 'fk_r1cs_load_coded', 'fk_r1cs_free', 'fk_r1cs_info', 'fk_r1cs_windows', 'fk_r1cs_density_ptrs', 'fk_r1cs_eval_dev', 'fk_r1cs_eval_slice_dev', 'fk_prove_r1cs', 'fk_prove_r1cs_dev',
-    'fk_init_devices', 'fk_multi_free', 'fk_multi_last_error', 'fk_multi_size', 'fk_multi_transport', 'fk_multi_topology', 'fk_multi_preflight', 'fk_multi_ctx', 'fk_multi_sync', 'fk_multi_witness_traffic',
-    'fk_multi_key_load', 'fk_multi_key_load_bellman', 'fk_multi_setup', 'fk_multi_setup_tiled', 'fk_multi_key_free', 'fk_multi_key_shard',
-    'fk_multi_r1cs_load', 'fk_multi_r1cs_load_tiled', 'fk_multi_r1cs_load_gates', 'fk_multi_r1cs_free', 'fk_multi_r1cs_replica',
-    'fk_multi_prove_r1cs', 'fk_multi_prove_r1cs_submit', 'fk_multi_prove_r1cs_wait',
-    'fk_poseidon_params_new', 'fk_poseidon_params_load', 'fk_poseidon_params_get', 'fk_poseidon_free',
-    'fk_poseidon_hash_batch', 'fk_poseidon_hash_batch_dev', 'fk_poseidon_sponge_batch',
-    'fk_poseidon_merkle_tree_dev', 'fk_poseidon_merkle_root', 'fk_poseidon_merkle_proofs_dev',
-    'fk_poseidon_merkle_proof_roots', 'fk_poseidon_merkle_proof_roots_dev',
-    'fk_jubjub_params', 'fk_jubjub_mul_batch', 'fk_jubjub_decompress_batch',
-    'fk_eddsa_hash_r', 'fk_eddsa_sign_batch', 'fk_eddsa_verify_batch', 'fk_eddsa_verify_batch_dev',
-]
+# every symbol include/fawkes_hip.h declares (tests check the .so exports all of them, and the table against the header)
+EXPORTED_SYMBOLS = list(_abi.PROTOTYPES)
 
 _ERR = {1: 'FK_ERR_BAD_ARG', 2: 'FK_ERR_DOMAIN_TOO_LARGE (bellman: PolynomialDegreeTooLarge)',
         3: 'FK_ERR_UNEXPECTED_IDENTITY (bellman: UnexpectedIdentity)', 4: 'FK_ERR_HIP', 5: 'FK_ERR_OOM',
@@ -63,6 +40,14 @@ class FkError(RuntimeError):
     def __init__(self, code, msg=''):
         self.code = code
         super().__init__('%s: %s' % (_ERR.get(code, 'error %d' % code), msg))
+
+
+def _check(rc, fallback='', last_error=None, handle=None):
+    """The one return-code check: FkError unless rc is FK_OK, with the library's text where there is a context to ask (last_error =
+    lib.fk_last_error / lib.fk_multi_last_error, about `handle`) and `fallback` (the function's name) where there is none."""
+    if rc != 0:
+        msg = last_error(handle) if last_error else None
+        raise FkError(rc, msg.decode() if msg else fallback)
 
 
 def lib_path():
@@ -79,44 +64,6 @@ def build_library(jobs=3):
 _LIB = None
 
 
-class KeyDesc(C.Structure):
-    _fields_ = [('m', C.c_uint64), ('num_input', C.c_uint32), ('num_aux', C.c_uint32),
-                ('alpha_g1', C.c_void_p), ('beta_g1', C.c_void_p), ('delta_g1', C.c_void_p),
-                ('beta_g2', C.c_void_p), ('delta_g2', C.c_void_p),
-                ('h', C.c_void_p), ('n_h', C.c_uint64), ('l', C.c_void_p), ('n_l', C.c_uint64),
-                ('a', C.c_void_p), ('n_a', C.c_uint64),
-                ('b_g1', C.c_void_p), ('b_g2', C.c_void_p), ('n_b', C.c_uint64),
-                ('shard_index', C.c_uint32), ('shard_count', C.c_uint32),
-                ('z_frac_lo', C.c_double), ('z_frac_hi', C.c_double)]
-
-
-class Timings(C.Structure):
-    _fields_ = [(n, C.c_double) for n in ('upload_ms', 'ntt_ms', 'msm_h_ms', 'msm_l_ms', 'msm_a_ms', 'msm_b1_ms',
-                                          'msm_b2_ms', 'assemble_ms', 'total_ms')]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
-
-
-class R1csStruct(C.Structure):
-    _fields_ = [('num_input', C.c_uint32), ('num_aux', C.c_uint32), ('num_gates', C.c_uint64),
-                ('a_ptr', C.c_void_p), ('a_col', C.c_void_p), ('a_val', C.c_void_p),
-                ('b_ptr', C.c_void_p), ('b_col', C.c_void_p), ('b_val', C.c_void_p),
-                ('c_ptr', C.c_void_p), ('c_col', C.c_void_p), ('c_val', C.c_void_p)]
-
-
-class MsmPlanInfo(C.Structure):
-    """fk_msm_plan_info: the window plan of one multiplication and the compile-time limits it is sized against"""
-    _fields_ = [('n', C.c_uint64), ('chunk', C.c_uint64)] + [(f, C.c_uint32) for f in (
-        'c', 'W', 'B', 'cb', 'wide', 'nchunks', 'cap', 'L', 'T', 'nblk', 'LB', 'nhi', 'nlo',
-        's1_tile', 's2_tile', 's2_max_hi', 'over_max', 'seg_min', 'seg_max', 'size_bins')]
-
-
-class MsmDynInfo(C.Structure):
-    """fk_msm_dyn_info: what the front of a multiplication decided on the device"""
-    _fields_ = [(f, C.c_uint32) for f in ('cap', 'n_over', 'seg', 'n_tasks', 'n_obs', 'error')] + [('adds', C.c_uint64)]
-
-
 def load_library():
     """Loads libfawkes_hip.so; raises if it has not been built (no fallback)."""
     global _LIB
@@ -125,34 +72,7 @@ def load_library():
         if not os.path.exists(p):
             raise FileNotFoundError('%s missing: run __graft_entry__.build() (hipcc, gfx950)' % p)
         lib = C.CDLL(p)
-        lib.fk_last_error.restype = C.c_char_p
-        lib.fk_last_error.argtypes = [C.c_void_p]
-        lib.fk_free.argtypes = [C.c_void_p]
-        lib.fk_free.restype = None
-        lib.fk_key_free.argtypes = [C.c_void_p, C.c_void_p]
-        lib.fk_key_free.restype = None
-        lib.fk_gates_free.argtypes = [C.c_void_p]
-        lib.fk_gates_free.restype = None
-        lib.fk_blob_free.argtypes = [C.c_void_p]
-        lib.fk_blob_free.restype = None
-        lib.fk_multi_last_error.restype = C.c_char_p
-        lib.fk_multi_last_error.argtypes = [C.c_void_p]
-        lib.fk_multi_free.argtypes = [C.c_void_p]
-        lib.fk_multi_free.restype = None
-        lib.fk_multi_key_free.argtypes = [C.c_void_p, C.c_void_p]
-        lib.fk_multi_key_free.restype = None
-        lib.fk_multi_r1cs_free.argtypes = [C.c_void_p, C.c_void_p]
-        lib.fk_multi_r1cs_free.restype = None
-        lib.fk_multi_transport.restype = C.c_char_p
-        lib.fk_multi_transport.argtypes = [C.c_void_p]
-        lib.fk_multi_ctx.restype = C.c_void_p
-        lib.fk_multi_ctx.argtypes = [C.c_void_p, C.c_int]
-        lib.fk_multi_key_shard.restype = C.c_void_p
-        lib.fk_multi_key_shard.argtypes = [C.c_void_p, C.c_int]
-        lib.fk_multi_r1cs_replica.restype = C.c_void_p
-        lib.fk_multi_r1cs_replica.argtypes = [C.c_void_p, C.c_int]
-        lib.fk_poseidon_free.argtypes = [C.c_void_p]
-        lib.fk_poseidon_free.restype = None
+        _abi.apply(lib)
         _LIB = lib
     return _LIB
 
@@ -160,7 +80,29 @@ def load_library():
 def _vp(arr):
     if arr is None:
         return None
-    return C.c_void_p(arr.ctypes.data)
+    return arr.ctypes.data
+
+
+class _Handle:
+    """Owner of one native handle.  A subclass says in _release(h) how the handle goes back to the library; free() calls it at most once
+    however often free() and __del__ run, never for a `borrowed` handle (one the library or another object owns), and is safe on an
+    object whose constructor raised before `handle` was set."""
+    handle = None
+    borrowed = False
+
+    def _release(self, h):
+        raise NotImplementedError
+
+    def free(self):
+        h, self.handle = self.handle, None          # taken out first: load_parameters frees a Gates on a background thread
+        if h and not self.borrowed:
+            self._release(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _fr(arr, rows=None):
@@ -416,15 +358,13 @@ class Parameters:
         return d
 
 
-class DeviceKey:
-    def __init__(self, ctx, handle, shard_index=0, shard_count=1):
-        self.ctx, self.handle = ctx, handle
+class DeviceKey(_Handle):
+    def __init__(self, ctx, handle, shard_index=0, shard_count=1, borrowed=False):
+        self.ctx, self.handle, self.borrowed = ctx, handle, borrowed
         self.shard_index, self.shard_count = shard_index, shard_count
 
-    def free(self):
-        if self.handle:
-            self.ctx.lib.fk_key_free(self.ctx.handle, self.handle)
-            self.handle = None
+    def _release(self, h):
+        self.ctx.lib.fk_key_free(self.ctx.handle, h)
 
     def download(self, name):
         """this key's slice of one array as numpy: 'h' | 'l' | 'a' | 'b_g1' (n,64) or 'b_g2' (n,128)"""
@@ -434,23 +374,19 @@ class DeviceKey:
         w = 128 if name == 'b_g2' else 64
         out = np.zeros((max(hi - lo, 0), w), np.uint8)
         buf = out if out.size else np.zeros((1, w), np.uint8)
-        self.ctx._ck(self.ctx.lib.fk_key_download(self.ctx.handle, self.handle, C.c_int(which), C.c_void_p(buf.ctypes.data), C.c_size_t(buf.nbytes)))
+        self.ctx._ck(self.ctx.lib.fk_key_download(self.ctx.handle, self.handle, which, buf.ctypes.data, buf.nbytes))
         return out
 
     def counts(self):
         out = (C.c_uint64 * 8)()
-        rc = self.ctx.lib.fk_key_counts(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_key_counts')
+        _check(self.ctx.lib.fk_key_counts(self.handle, out), 'fk_key_counts')
         v = list(out)
         return dict(m=v[0], num_input=v[1], num_aux=v[2], n_h=v[3], n_l=v[4], n_a=v[5], n_b=v[6], shard_count=v[7])
 
     def precomputed(self):
         """fk_key_precomputed: window levels held per array (0 = the ordinary W-bucket-set path)"""
         out = (C.c_uint32 * 5)()
-        rc = self.ctx.lib.fk_key_precomputed(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_key_precomputed')
+        _check(self.ctx.lib.fk_key_precomputed(self.handle, out), 'fk_key_precomputed')
         return dict(zip(('h', 'l', 'a', 'b_g1', 'b_g2'), list(out)))
 
     def levels_headroom(self):
@@ -482,44 +418,33 @@ class DeviceKey:
     def vk(self):
         """prover-side vk points as raw Montgomery LE uint8 arrays"""
         buf = np.zeros(3 * 64 + 2 * 128, np.uint8)
-        rc = self.ctx.lib.fk_key_vk(self.handle, C.c_void_p(buf.ctypes.data))
-        if rc != 0:
-            raise FkError(rc, 'fk_key_vk')
+        _check(self.ctx.lib.fk_key_vk(self.handle, buf.ctypes.data), 'fk_key_vk')
         return dict(alpha_g1=buf[0:64].copy(), beta_g1=buf[64:128].copy(), delta_g1=buf[128:192].copy(),
                     beta_g2=buf[192:320].copy(), delta_g2=buf[320:448].copy())
 
     def shard_info(self):
         """dict of the [lo, hi) slices this key holds: h, l, a, b"""
         out = (C.c_uint64 * 8)()
-        rc = self.ctx.lib.fk_key_shard_info(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_key_shard_info')
+        _check(self.ctx.lib.fk_key_shard_info(self.handle, out), 'fk_key_shard_info')
         v = list(out)
         out2 = (C.c_uint64 * 10)()
-        rc = self.ctx.lib.fk_key_shard_info2(self.handle, out2)
-        if rc != 0:
-            raise FkError(rc, 'fk_key_shard_info2')
+        _check(self.ctx.lib.fk_key_shard_info2(self.handle, out2), 'fk_key_shard_info2')
         w = list(out2)
         return dict(h=(v[0], v[1]), l=(v[2], v[3]), a=(v[4], v[5]), b=(v[6], v[7]), b_g2=(w[8], w[9]))
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
-
-class DeviceR1cs:
+class DeviceR1cs(_Handle):
     """Constraint system resident in HBM (fk_r1cs_load): CSR + coefficient dictionary + density maps."""
 
-    def __init__(self, ctx, handle):
-        self.ctx, self.handle = ctx, handle
+    def __init__(self, ctx, handle, borrowed=False):
+        self.ctx, self.handle, self.borrowed = ctx, handle, borrowed
+
+    def _release(self, h):
+        self.ctx.lib.fk_r1cs_free(self.ctx.handle, h)
 
     def info(self):
         out = (C.c_uint64 * 8)()
-        rc = self.ctx.lib.fk_r1cs_info(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_r1cs_info')
+        _check(self.ctx.lib.fk_r1cs_info(self.handle, out), 'fk_r1cs_info')
         v = list(out)
         return dict(rows=v[0], nnz=(v[1], v[2], v[3]), distinct_coefficients=v[4], n_a=v[5], n_b=v[6], num_vars=v[7])
 
@@ -527,9 +452,7 @@ class DeviceR1cs:
         """row windows of the chunked witness hand-over (fk_r1cs_windows): dict(rows=[K + 1 gate bounds], need=[K witness prefixes]) or None"""
         k = C.c_uint32(0)
         rows, need = (C.c_uint64 * 17)(), (C.c_uint64 * 16)()
-        rc = self.ctx.lib.fk_r1cs_windows(self.handle, C.byref(k), rows, need)
-        if rc != 0:
-            raise FkError(rc, 'fk_r1cs_windows')
+        _check(self.ctx.lib.fk_r1cs_windows(self.handle, C.byref(k), rows, need), 'fk_r1cs_windows')
         if not k.value:
             return None
         return dict(rows=list(rows)[:k.value + 1], need=list(need)[:k.value])
@@ -544,21 +467,8 @@ class DeviceR1cs:
     def density_ptrs(self):
         """device pointers (a_aux, b_input, b_aux) of the structural density maps"""
         out = (C.c_void_p * 3)()
-        rc = self.ctx.lib.fk_r1cs_density_ptrs(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_r1cs_density_ptrs')
+        _check(self.ctx.lib.fk_r1cs_density_ptrs(self.handle, out), 'fk_r1cs_density_ptrs')
         return tuple(int(x or 0) for x in out)
-
-    def free(self):
-        if self.handle:
-            self.ctx.lib.fk_r1cs_free(self.ctx.handle, self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 FK_GATES_RAW, FK_GATES_BROTLI = 0, 1
@@ -572,18 +482,34 @@ def _bytes_view(data):
     return np.frombuffer(data, np.uint8)
 
 
-class GateBlob:
+_VK_SLOTS = (('alpha_g1', 64), ('beta_g1', 64), ('beta_g2', 128), ('gamma_g2', 128), ('delta_g1', 64), ('delta_g2', 128))
+_IC_CAP = 1 << 16
+
+
+def _vk_dict(vk, ic):
+    """the vk dict of Context.setup / MultiContext.setup from the six 128-byte slots fk_setup* filled (G1 points use the first 64 bytes)"""
+    out = {n: vk[i * 128:i * 128 + w].copy() for i, (n, w) in enumerate(_VK_SLOTS)}
+    out['ic'] = ic
+    return out
+
+
+def _load_bellman(ck, loader, *head):
+    """runs one of the two bellman key loaders: `head` is its argument list up to `out`, the tail (out, gamma_g2_out, ic_out, ic_cap,
+    n_ic) is made here; returns (key handle, gamma_g2, the ic points the file held)"""
+    h, n_ic = C.c_void_p(), C.c_uint32()
+    gamma, ic = np.zeros(128, np.uint8), np.zeros((_IC_CAP, 64), np.uint8)
+    ck(loader(*head, C.byref(h), _vp(gamma), _vp(ic), _IC_CAP, C.byref(n_ic)))
+    return h, gamma, ic[:min(n_ic.value, _IC_CAP)].copy()
+
+
+class GateBlob(_Handle):
     """fk_blob: the gate blob of a `Parameters` object as fk_gates_encode wrote it (host memory owned by the library).
     `.data` is a uint8 view valid until free()."""
 
     def __init__(self, r1cs, copies=None, fmt=1, quality=9, lgwin=22, ctx=None):
         self.lib = load_library()
-        h = C.c_void_p()
-        rc = self.lib.fk_gates_encode(ctx.handle if ctx else None, C.byref(r1cs.struct), C.c_uint32(int(copies or 1)), C.c_int(fmt), C.c_int(quality),
-                                      C.c_int(lgwin), C.byref(h))
-        if rc != 0:
-            msg = self.lib.fk_last_error(ctx.handle if ctx else None)
-            raise FkError(rc, msg.decode() if msg else 'fk_gates_encode')
+        h, ch = C.c_void_p(), ctx.handle if ctx else None
+        _check(self.lib.fk_gates_encode(ch, C.byref(r1cs.struct), int(copies or 1), fmt, quality, lgwin, C.byref(h)), 'fk_gates_encode', self.lib.fk_last_error, ch)
         self.handle = h
         p, n = C.c_void_p(), C.c_size_t()
         self.lib.fk_blob_data(h, C.byref(p), C.byref(n))
@@ -597,48 +523,36 @@ class GateBlob:
         return dict(wall_s=v[0], compressor_s=v[1], stream_bytes=int(v[2]), blob_bytes=int(v[3]))
 
     def free(self):
-        if getattr(self, 'handle', None):
-            self.data = None
-            self.lib.fk_blob_free(self.handle)
-            self.handle = None
+        if self.handle:
+            self.data = None            # the view goes before the memory behind it
+        super().free()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, h):
+        self.lib.fk_blob_free(h)
 
 
-class Gates:
+class Gates(_Handle):
     """fk_gates: the constraint system decoded from the gate blob of a `Parameters` file (host memory, native decoder).
     fmt: FK_GATES_BROTLI (what the reference writes, setup.rs:25-32) or FK_GATES_RAW (the bare Borsh gate stream)."""
 
     def __init__(self, blob, fmt, num_gates, num_input, num_aux, ctx=None):
         self.lib = load_library()
         buf = _bytes_view(blob)              # no copy: a benchmark-size blob is GBs
-        h = C.c_void_p()
-        rc = self.lib.fk_gates_decode(ctx.handle if ctx else None, _vp(buf), C.c_size_t(buf.size), C.c_int(fmt), C.c_uint32(num_gates),
-                                      C.c_uint32(num_input), C.c_uint32(num_aux), C.byref(h))
-        if rc != 0:
-            msg = self.lib.fk_last_error(ctx.handle if ctx else None)
-            raise FkError(rc, msg.decode() if msg else 'fk_gates_decode')
+        h, ch = C.c_void_p(), ctx.handle if ctx else None
+        _check(self.lib.fk_gates_decode(ch, _vp(buf), buf.size, fmt, num_gates, num_input, num_aux, C.byref(h)), 'fk_gates_decode', self.lib.fk_last_error, ch)
         self.handle = h
 
     def profile(self):
         """fk_gates_profile: how the decoding went (seconds; the decompressor is the serial floor, the parsing runs beside it)"""
         out = (C.c_double * 8)()
-        rc = self.lib.fk_gates_profile(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_gates_profile')
+        _check(self.lib.fk_gates_profile(self.handle, out), 'fk_gates_profile')
         v = list(out)
         return dict(wall_s=v[0], decompressor_s=v[1], waited_for_parsers_s=v[2], parse_cpu_s=v[3], renumber_s=v[4], parse_threads=int(v[5]),
                     blocks=int(v[6]), blob_bytes=int(v[7]))
 
     def info(self):
         out = (C.c_uint64 * 8)()
-        rc = self.lib.fk_gates_info(self.handle, out)
-        if rc != 0:
-            raise FkError(rc, 'fk_gates_info')
+        _check(self.lib.fk_gates_info(self.handle, out), 'fk_gates_info')
         v = list(out)
         return dict(num_gates=v[0], nnz=(v[1], v[2], v[3]), distinct_coefficients=v[4], decoded_bytes=v[5], num_input=v[6], num_aux=v[7])
 
@@ -650,9 +564,7 @@ class Gates:
             ptr = np.zeros(i['num_gates'] + 1, np.uint64)
             col = np.zeros(max(i['nnz'][k], 1), np.uint32)[:i['nnz'][k]]
             val = np.zeros((max(i['nnz'][k], 1), 4), np.uint64)[:i['nnz'][k]]
-            rc = self.lib.fk_gates_export(self.handle, C.c_int(k), _vp(ptr), C.c_void_p(col.ctypes.data), C.c_void_p(val.ctypes.data))
-            if rc != 0:
-                raise FkError(rc, 'fk_gates_export')
+            _check(self.lib.fk_gates_export(self.handle, k, _vp(ptr), col.ctypes.data, val.ctypes.data), 'fk_gates_export')
             mats.append((ptr, col, val))
         return R1cs(i['num_input'], i['num_aux'], *mats)
 
@@ -662,38 +574,22 @@ class Gates:
         ctx._ck(ctx.lib.fk_r1cs_load_gates(ctx.handle, self.handle, C.byref(h)))
         return DeviceR1cs(ctx, h)
 
-    def free(self):
-        h, self.handle = getattr(self, 'handle', None), None          # (taken first: load_parameters frees on a background thread)
-        if h:
-            self.lib.fk_gates_free(h)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, h):
+        self.lib.fk_gates_free(h)
 
 
-class HostVk:
+class HostVk(_Handle):
     """Host-only key (vk points only) for fk_prove_assemble -- needs no GPU."""
 
     def __init__(self, params):
         self.lib = load_library()
         h = C.c_void_p()
         v = params.vk
-        rc = self.lib.fk_key_host_vk(_vp(v['alpha_g1']), _vp(v['beta_g1']), _vp(v['delta_g1']), _vp(v['beta_g2']),
-                                     _vp(v['delta_g2']), C.byref(h))
-        if rc != 0:
-            raise FkError(rc, 'fk_key_host_vk')
+        _check(self.lib.fk_key_host_vk(_vp(v['alpha_g1']), _vp(v['beta_g1']), _vp(v['delta_g1']), _vp(v['beta_g2']), _vp(v['delta_g2']), C.byref(h)), 'fk_key_host_vk')
         self.handle = h
 
-    def __del__(self):
-        try:
-            if self.handle:
-                self.lib.fk_key_free(None, self.handle)
-                self.handle = None
-        except Exception:
-            pass
+    def _release(self, h):
+        self.lib.fk_key_free(None, h)
 
 
 _FR_RINV = pow(1 << 256, -1, FR_MODULUS)
@@ -721,18 +617,15 @@ def _fr_ints(limbs):
     return [limbs_to_int(row) * _FR_RINV % FR_MODULUS for row in np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)]
 
 
-class PoseidonParams:
+class PoseidonParams(_Handle):
     """native/poseidon.rs:15-49: PoseidonParams::new_with_salt(t, f, p, salt), generated by the library on the host (fk_poseidon_params_new;
     no GPU needed).  `.c` ((f + p) rows of t) and `.m` (t rows of t) are canonical ints."""
 
     def __init__(self, t, f, p, salt='', _handle=None):
         self.lib = load_library()
-        self.handle = None
         if _handle is None:
             _handle = C.c_void_p()
-            rc = self.lib.fk_poseidon_params_new(C.c_uint32(t), C.c_uint32(f), C.c_uint32(p), C.c_char_p(salt.encode()), C.byref(_handle))
-            if rc != 0:
-                raise FkError(rc, (self.lib.fk_last_error(None) or b'').decode())
+            _check(self.lib.fk_poseidon_params_new(t, f, p, salt.encode(), C.byref(_handle)), '', self.lib.fk_last_error)
         self.handle = _handle
         self.t, self.f, self.p = int(t), int(f), int(p)
 
@@ -744,9 +637,7 @@ class PoseidonParams:
         if not (isinstance(t, int) and isinstance(f, int) and isinstance(p, int)) or min(t, f, p) < 0 or max(t, f, p) >= 1 << 32:
             raise FkError(1, 'poseidon: t, f, p must be small non-negative integers')
         ca, ma = _fr_rows(c, (f + p) * t), _fr_rows(m, t * t)
-        rc = lib.fk_poseidon_params_load(C.c_uint32(t), C.c_uint32(f), C.c_uint32(p), _vp(ca), _vp(ma), C.byref(h))
-        if rc != 0:
-            raise FkError(rc, (lib.fk_last_error(None) or b'').decode())
+        _check(lib.fk_poseidon_params_load(t, f, p, _vp(ca), _vp(ma), C.byref(h)), '', lib.fk_last_error)
         return cls(t, f, p, _handle=h)
 
     def limbs(self):
@@ -755,8 +646,7 @@ class PoseidonParams:
         c = np.zeros((self.f + self.p, self.t, 4), np.uint64)
         m = np.zeros((self.t, self.t, 4), np.uint64)
         rc = self.lib.fk_poseidon_params_get(self.handle, dims, _vp(c), _vp(m))
-        if rc != 0 or tuple(dims) != (self.t, self.f, self.p):
-            raise FkError(rc or 1, 'fk_poseidon_params_get')
+        _check(rc or int(tuple(dims) != (self.t, self.f, self.p)), 'fk_poseidon_params_get')
         return c, m
 
     @property
@@ -769,16 +659,8 @@ class PoseidonParams:
         v = _fr_ints(self.limbs()[1])
         return [v[i * self.t:(i + 1) * self.t] for i in range(self.t)]
 
-    def free(self):
-        if getattr(self, 'handle', None):
-            self.lib.fk_poseidon_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, h):
+        self.lib.fk_poseidon_free(h)
 
 
 FS_MODULUS = 2736030358979909402780800718157159386076813972158567259200215660948447373041      # the JubJub scalar field (251 bits)
@@ -813,9 +695,7 @@ def jubjub_params():
     """JubJubBN256 (engines/bn256/mod.rs:48-75) as the library derived it on the host: dict(d, g=(x, y), fs), canonical ints"""
     lib = load_library()
     d, g, fs = np.zeros(4, np.uint64), np.zeros(8, np.uint64), np.zeros(4, np.uint64)
-    rc = lib.fk_jubjub_params(_vp(d), _vp(g), _vp(fs))
-    if rc != 0:
-        raise FkError(rc, (lib.fk_last_error(None) or b'').decode())
+    _check(lib.fk_jubjub_params(_vp(d), _vp(g), _vp(fs)), '', lib.fk_last_error)
     gx, gy = _fr_ints(g)
     return dict(d=_fr_ints(d)[0], g=(gx, gy), fs=limbs_to_int(fs))
 
@@ -825,19 +705,19 @@ def eddsa_hash_r(sk, m):
     m: a canonical int (or 4 Montgomery limbs).  Ints in give an int, limbs give limbs.  Host only."""
     lib = load_library()
     ka, ma, out = _u256_rows(sk, 1), _fr_rows(m, 1), np.zeros(4, np.uint64)
-    rc = lib.fk_eddsa_hash_r(_vp(ka), _vp(ma), _vp(out))
-    if rc != 0:
-        raise FkError(rc, (lib.fk_last_error(None) or b'').decode())
+    _check(lib.fk_eddsa_hash_r(_vp(ka), _vp(ma), _vp(out)), '', lib.fk_last_error)
     return out if _is_limbs(sk) and _is_limbs(m) else limbs_to_int(out)
 
 
-class MerkleTree:
+class MerkleTree(_Handle):
     """A Poseidon Merkle tree resident in device memory (Context.merkle_tree): 2^(depth + 1) - 1 nodes, the leaves (zero-padded to
-    2^depth) first, the root last."""
+    2^depth) first, the root last.  The handle is `d_nodes`, the device pointer of the node array (None once freed)."""
 
     def __init__(self, ctx, d_nodes, depth, n_leaves):
-        self.ctx, self.d_nodes, self.depth, self.n_leaves = ctx, d_nodes, depth, n_leaves
+        self.ctx, self.handle, self.depth, self.n_leaves = ctx, d_nodes, depth, n_leaves
         self._root = None
+
+    d_nodes = property(lambda self: self.handle)
 
     @property
     def n_nodes(self):
@@ -865,76 +745,59 @@ class MerkleTree:
         d_sib = ctx.dev_alloc(max(32 * n * self.depth, 32))
         try:
             ctx.upload(d_idx, idx)
-            ctx._ck(ctx.lib.fk_poseidon_merkle_proofs_dev(ctx.handle, C.c_void_p(self.d_nodes), C.c_uint32(self.depth), C.c_void_p(d_idx), C.c_size_t(n),
-                                                          C.c_void_p(d_sib)))
+            ctx._ck(ctx.lib.fk_poseidon_merkle_proofs_dev(ctx.handle, self.d_nodes, self.depth, d_idx, n, d_sib))
             flat = _fr_ints(ctx.download(d_sib, 32 * n * self.depth, np.uint64)) if self.depth else []
         finally:
             ctx.dev_free(d_idx)
             ctx.dev_free(d_sib)
         return [flat[i * self.depth:(i + 1) * self.depth] for i in range(n)], [int(i) for i in idx]
 
-    def free(self):
-        if getattr(self, 'd_nodes', None) and getattr(self.ctx, 'handle', None):
-            self.ctx.dev_free(self.d_nodes)
-        self.d_nodes = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, d_nodes):
+        if self.ctx.handle:             # a closed context has released its device memory itself
+            self.ctx.dev_free(d_nodes)
 
 
-class Context:
+class Context(_Handle):
     """One GPU (one process per GPU for multi-GPU runs).  Raises FkError if no GPU is usable."""
     _window_bits = 0          # what set_window_bits last asked for (msm_front_dump sizes its buffers from it)
 
     def __init__(self, device_id=0, _borrowed=None):
         self.lib = load_library()
         self.device_id = device_id
-        self._owned = _borrowed is None
-        if _borrowed is not None:           # a rank's context of a MultiContext: owned by the fk_multi
-            self.handle = C.c_void_p(_borrowed)
+        self._pinned, self._tickets = {}, {}      # host_alloc's buffers; what the outstanding prove_witness_submit tickets keep alive
+        self.borrowed = _borrowed is not None
+        if self.borrowed:                   # a rank's context of a MultiContext: owned by the fk_multi, never passed to fk_free
+            self.handle = _borrowed
             return
         h = C.c_void_p()
-        rc = self.lib.fk_init(C.c_int(device_id), C.byref(h))
-        if rc != 0:
-            raise FkError(rc, 'fk_init(device %d) failed -- no usable MI355X/HIP device; there is no CPU fallback' % device_id)
+        _check(self.lib.fk_init(device_id, C.byref(h)), 'fk_init(device %d) failed -- no usable MI355X/HIP device; there is no CPU fallback' % device_id)
         self.handle = h
 
-    def close(self):
-        if getattr(self, 'handle', None):
-            if self._owned:
-                self.lib.fk_free(self.handle)
-            self.handle = None
+    def _release(self, h):
+        self.lib.fk_free(h)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def close(self):
+        self.free()
 
     def _ck(self, rc):
-        if rc != 0:
-            msg = self.lib.fk_last_error(self.handle)
-            raise FkError(rc, msg.decode() if msg else '')
+        _check(rc, '', self.lib.fk_last_error, self.handle)
 
     # ---- device memory
     def dev_alloc(self, nbytes):
         p = C.c_void_p()
-        self._ck(self.lib.fk_dev_alloc(self.handle, C.c_size_t(nbytes), C.byref(p)))
+        self._ck(self.lib.fk_dev_alloc(self.handle, nbytes, C.byref(p)))
         return p.value
 
     def dev_free(self, dptr):
-        self._ck(self.lib.fk_dev_free(self.handle, C.c_void_p(dptr)))
+        self._ck(self.lib.fk_dev_free(self.handle, dptr))
 
     def upload(self, dptr, arr):
         arr = np.ascontiguousarray(arr)
-        self._ck(self.lib.fk_upload(self.handle, C.c_void_p(dptr), _vp(arr), C.c_size_t(arr.nbytes)))
+        self._ck(self.lib.fk_upload(self.handle, dptr, _vp(arr), arr.nbytes))
 
     def download(self, dptr, nbytes, dtype=np.uint8):
         out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype)
-        self._ck(self.lib.fk_download(self.handle, _vp(out), C.c_void_p(dptr), C.c_size_t(nbytes)))
+        self._ck(self.lib.fk_download(self.handle, _vp(out), dptr, nbytes))
         return out
 
     def sync(self):
@@ -955,41 +818,40 @@ class Context:
         """fk_host_alloc: a numpy array over pinned host memory (free with host_free(arr))."""
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = C.c_void_p()
-        self._ck(self.lib.fk_host_alloc(self.handle, C.c_size_t(n), C.byref(p)))
+        self._ck(self.lib.fk_host_alloc(self.handle, n, C.byref(p)))
         arr = np.frombuffer((C.c_uint8 * max(n, 1)).from_address(p.value), dtype=np.uint8, count=n).view(dtype).reshape(shape)
-        self._pinned = getattr(self, '_pinned', {})
         self._pinned[arr.ctypes.data] = p.value
         return arr
 
     def host_free(self, arr):
-        p = getattr(self, '_pinned', {}).pop(arr.ctypes.data, None)
+        p = self._pinned.pop(arr.ctypes.data, None)
         if p is not None:
-            self._ck(self.lib.fk_host_free(self.handle, C.c_void_p(p)))
+            self._ck(self.lib.fk_host_free(self.handle, p))
 
     def witness_upload_async(self, slot, z):
         """fk_witness_upload_async: z must stay alive (and should be pinned) until the proof that reads the slot returns"""
         assert z.flags['C_CONTIGUOUS']
-        self._ck(self.lib.fk_witness_upload_async(self.handle, C.c_int(slot), _vp(z), C.c_size_t(z.nbytes)))
+        self._ck(self.lib.fk_witness_upload_async(self.handle, slot, _vp(z), z.nbytes))
 
     def witness_ptr(self, slot):
         p = C.c_void_p()
-        self._ck(self.lib.fk_witness_ptr(self.handle, C.c_int(slot), C.byref(p)))
+        self._ck(self.lib.fk_witness_ptr(self.handle, slot, C.byref(p)))
         return p.value
 
     # ---- the sharded hand-over: a rank uploads its own piece, the ranks all-gather the rest (parallel.witness_all_gather)
     def witness_slot(self, slot, total_bytes):
         """fk_witness_slot: (device pointer of the slot with room for total_bytes, hipStream_t of the copy stream as an integer)"""
         p, st = C.c_void_p(), C.c_void_p()
-        self._ck(self.lib.fk_witness_slot(self.handle, C.c_int(slot), C.c_size_t(total_bytes), C.byref(p), C.byref(st)))
+        self._ck(self.lib.fk_witness_slot(self.handle, slot, total_bytes, C.byref(p), C.byref(st)))
         return p.value or 0, st.value or 0
 
     def witness_upload_part_async(self, slot, part, offset):
         """fk_witness_upload_part_async: `part` (contiguous array; pinned memory overlaps) -> slot bytes [offset, offset + part.nbytes)"""
         assert part.flags['C_CONTIGUOUS']
-        self._ck(self.lib.fk_witness_upload_part_async(self.handle, C.c_int(slot), _vp(part) if part.nbytes else None, C.c_size_t(offset), C.c_size_t(part.nbytes)))
+        self._ck(self.lib.fk_witness_upload_part_async(self.handle, slot, _vp(part) if part.nbytes else None, offset, part.nbytes))
 
     def witness_mark_ready(self, slot):
-        self._ck(self.lib.fk_witness_mark_ready(self.handle, C.c_int(slot)))
+        self._ck(self.lib.fk_witness_mark_ready(self.handle, slot))
 
     def prove_witness_submit(self, key, dr, z, r, s):
         """fk_prove_r1cs_submit -> ticket.  z, r, s are kept referenced until prove_witness_wait(ticket)."""
@@ -998,7 +860,6 @@ class Context:
         r, s = _fr(r, 1), _fr(s, 1)
         t = C.c_int(-1)
         self._ck(self.lib.fk_prove_r1cs_submit(self.handle, key.handle, dr.handle, _vp(z), _vp(r), _vp(s), C.byref(t)))
-        self._tickets = getattr(self, '_tickets', {})
         self._tickets[t.value] = (z, r, s, key, dr)
         return t.value
 
@@ -1006,13 +867,13 @@ class Context:
         out = np.zeros(FK_PROOF_BYTES, np.uint8)
         tm = Timings()
         try:
-            self._ck(self.lib.fk_prove_r1cs_wait(self.handle, C.c_int(ticket), _vp(out), C.byref(tm)))
+            self._ck(self.lib.fk_prove_r1cs_wait(self.handle, ticket, _vp(out), C.byref(tm)))
         finally:
-            getattr(self, '_tickets', {}).pop(ticket, None)
+            self._tickets.pop(ticket, None)
         return (out, tm.as_dict()) if want_timings else out
 
     def set_window_bits(self, c):
-        self._ck(self.lib.fk_set_window_bits(self.handle, C.c_uint(c)))
+        self._ck(self.lib.fk_set_window_bits(self.handle, c))
         self._window_bits = c
 
     # ---- keys
@@ -1024,16 +885,14 @@ class Context:
 
     def synthetic_key(self, m, num_input, num_aux, n_a, n_b, seed=1, shard_index=0, shard_count=1, z_frac=Z_EQUAL_SPLIT):
         h = C.c_void_p()
-        self._ck(self.lib.fk_key_synthetic(self.handle, C.c_uint64(m), C.c_uint32(num_input), C.c_uint32(num_aux),
-                                           C.c_uint64(n_a), C.c_uint64(n_b), C.c_uint64(seed), C.c_uint32(shard_index),
-                                           C.c_uint32(shard_count), C.c_double(z_frac[0]), C.c_double(z_frac[1]), C.byref(h)))
+        self._ck(self.lib.fk_key_synthetic(self.handle, m, num_input, num_aux, n_a, n_b, seed, shard_index, shard_count, z_frac[0], z_frac[1], C.byref(h)))
         return DeviceKey(self, h, shard_index, shard_count)
 
     # ---- building blocks (host arrays)
     def fr_mul_batch(self, a, b):
         a, b = _fr(a), _fr(b, None)
         out = np.zeros_like(a)
-        self._ck(self.lib.fk_fr_mul_batch(self.handle, _vp(a), _vp(b), _vp(out), C.c_size_t(a.shape[0])))
+        self._ck(self.lib.fk_fr_mul_batch(self.handle, _vp(a), _vp(b), _vp(out), a.shape[0]))
         return out
 
     def ntt(self, data, inverse=False, coset=False):
@@ -1041,11 +900,11 @@ class Context:
         log_n = int(d.shape[0]).bit_length() - 1
         if (1 << log_n) != d.shape[0]:
             raise FkError(1, 'ntt size must be a power of two')
-        self._ck(self.lib.fk_ntt(self.handle, _vp(d), C.c_uint32(log_n), C.c_int(int(inverse)), C.c_int(int(coset))))
+        self._ck(self.lib.fk_ntt(self.handle, _vp(d), log_n, int(inverse), int(coset)))
         return d
 
     def ntt_dev(self, dptr, log_n, inverse=False, coset=False):
-        self._ck(self.lib.fk_ntt_dev(self.handle, C.c_void_p(dptr), C.c_uint32(log_n), C.c_int(int(inverse)), C.c_int(int(coset))))
+        self._ck(self.lib.fk_ntt_dev(self.handle, dptr, log_n, int(inverse), int(coset)))
 
     def quotient_h(self, a, b, c):
         a, b, c = _fr(a), _fr(b), _fr(c)
@@ -1055,50 +914,47 @@ class Context:
             m *= 2
         h = np.zeros((max(m - 1, 0), 4), np.uint64)
         hbuf = h if m > 1 else np.zeros((1, 4), np.uint64)
-        self._ck(self.lib.fk_quotient_h(self.handle, _vp(a), _vp(b), _vp(c), C.c_uint64(n), _vp(hbuf)))
+        self._ck(self.lib.fk_quotient_h(self.handle, _vp(a), _vp(b), _vp(c), n, _vp(hbuf)))
         return h
 
     def quotient_h_dev(self, d_a, d_b, d_c, n, d_h):
-        self._ck(self.lib.fk_quotient_h_dev(self.handle, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c), C.c_uint64(n), C.c_void_p(d_h)))
+        self._ck(self.lib.fk_quotient_h_dev(self.handle, d_a, d_b, d_c, n, d_h))
 
     # distributed quotient building blocks (include/fawkes_hip.h: fk_dq_*); world = 2^log_w ranks
     def dq_gather_dev(self, d_full, n, log_m, rank, log_w, d_local):
-        self._ck(self.lib.fk_dq_gather_dev(self.handle, C.c_void_p(d_full), C.c_uint64(n), C.c_uint32(log_m), C.c_uint32(rank),
-                                           C.c_uint32(log_w), C.c_void_p(d_local)))
+        self._ck(self.lib.fk_dq_gather_dev(self.handle, d_full, n, log_m, rank, log_w, d_local))
 
     def dq_local_dev(self, d_x, log_m, rank, log_w, stage, d_xb=0, d_xc=0):
-        self._ck(self.lib.fk_dq_local_dev(self.handle, C.c_void_p(d_x), C.c_void_p(d_xb), C.c_void_p(d_xc), C.c_uint32(log_m),
-                                          C.c_uint32(rank), C.c_uint32(log_w), C.c_int(stage)))
+        self._ck(self.lib.fk_dq_local_dev(self.handle, d_x, d_xb, d_xc, log_m, rank, log_w, stage))
 
     def dq_cross_dev(self, d_buf, log_m, rank, log_w, mode):
-        self._ck(self.lib.fk_dq_cross_dev(self.handle, C.c_void_p(d_buf), C.c_uint32(log_m), C.c_uint32(rank), C.c_uint32(log_w),
-                                          C.c_int(mode)))
+        self._ck(self.lib.fk_dq_cross_dev(self.handle, d_buf, log_m, rank, log_w, mode))
 
     def dq_cross_sub_dev(self, d_buf, d_sub, log_m, rank, log_w):
-        self._ck(self.lib.fk_dq_cross_sub_dev(self.handle, C.c_void_p(d_buf), C.c_void_p(d_sub), C.c_uint32(log_m), C.c_uint32(rank), C.c_uint32(log_w)))
+        self._ck(self.lib.fk_dq_cross_sub_dev(self.handle, d_buf, d_sub, log_m, rank, log_w))
 
     def msm_g1(self, bases, scalars):
         bases = np.ascontiguousarray(bases, np.uint8).reshape(-1, 64)
         scalars = _fr(scalars, bases.shape[0])
         out = np.zeros(64, np.uint8)
-        self._ck(self.lib.fk_msm_g1(self.handle, _vp(bases), _vp(scalars), C.c_size_t(bases.shape[0]), _vp(out)))
+        self._ck(self.lib.fk_msm_g1(self.handle, _vp(bases), _vp(scalars), bases.shape[0], _vp(out)))
         return out
 
     def msm_g2(self, bases, scalars):
         bases = np.ascontiguousarray(bases, np.uint8).reshape(-1, 128)
         scalars = _fr(scalars, bases.shape[0])
         out = np.zeros(128, np.uint8)
-        self._ck(self.lib.fk_msm_g2(self.handle, _vp(bases), _vp(scalars), C.c_size_t(bases.shape[0]), _vp(out)))
+        self._ck(self.lib.fk_msm_g2(self.handle, _vp(bases), _vp(scalars), bases.shape[0], _vp(out)))
         return out
 
     def msm_g1_dev(self, d_bases, d_scalars, n):
         out = np.zeros(64, np.uint8)
-        self._ck(self.lib.fk_msm_g1_dev(self.handle, C.c_void_p(d_bases), C.c_void_p(d_scalars), C.c_size_t(n), _vp(out)))
+        self._ck(self.lib.fk_msm_g1_dev(self.handle, d_bases, d_scalars, n, _vp(out)))
         return out
 
     def msm_g2_dev(self, d_bases, d_scalars, n):
         out = np.zeros(128, np.uint8)
-        self._ck(self.lib.fk_msm_g2_dev(self.handle, C.c_void_p(d_bases), C.c_void_p(d_scalars), C.c_size_t(n), _vp(out)))
+        self._ck(self.lib.fk_msm_g2_dev(self.handle, d_bases, d_scalars, n, _vp(out)))
         return out
 
     # ---- inspection of the multiplication's front (tests)
@@ -1125,9 +981,9 @@ class Context:
         try:
             if n:
                 self.upload(d_s, scalars)
-            self._ck(self.lib.fk_msm_front_dump(self.handle, C.c_void_p(d_s), C.c_size_t(n), C.c_int(int(merged)), _vp(out['digits']), _vp(out['sorted']),
-                                                _vp(out['totals']), _vp(out['starts']), _vp(perm), C.byref(dyn), _vp(tasks), C.c_size_t(tasks_cap),
-                                                _vp(obs), C.c_size_t(obs_cap)))
+            self._ck(self.lib.fk_msm_front_dump(self.handle, d_s, n, int(merged), _vp(out['digits']), _vp(out['sorted']),
+                                                _vp(out['totals']), _vp(out['starts']), _vp(perm), C.byref(dyn), _vp(tasks), tasks_cap,
+                                                _vp(obs), obs_cap))
         finally:
             self.dev_free(d_s)
         out['dyn'] = {f: int(getattr(dyn, f)) for f, _ in MsmDynInfo._fields_}
@@ -1138,13 +994,13 @@ class Context:
         return out
 
     def gen_points_g1_dev(self, dptr, n, seed):
-        self._ck(self.lib.fk_gen_points_g1_dev(self.handle, C.c_void_p(dptr), C.c_size_t(n), C.c_uint64(seed)))
+        self._ck(self.lib.fk_gen_points_g1_dev(self.handle, dptr, n, seed))
 
     def gen_points_g2_dev(self, dptr, n, seed):
-        self._ck(self.lib.fk_gen_points_g2_dev(self.handle, C.c_void_p(dptr), C.c_size_t(n), C.c_uint64(seed)))
+        self._ck(self.lib.fk_gen_points_g2_dev(self.handle, dptr, n, seed))
 
     def gen_scalars_dev(self, dptr, n, seed, kind=0):
-        self._ck(self.lib.fk_gen_scalars_dev(self.handle, C.c_void_p(dptr), C.c_size_t(n), C.c_uint64(seed), C.c_int(kind)))
+        self._ck(self.lib.fk_gen_scalars_dev(self.handle, dptr, n, seed, kind))
 
     # ---- synthesis + proving
     def synthesize(self, r1cs, z):
@@ -1158,8 +1014,8 @@ class Context:
         a_aux, b_in, b_aux, r, s = _u8(a_aux), _u8(b_in), _u8(b_aux), _fr(r, 1), _fr(s, 1)
         out = np.zeros(FK_PROOF_BYTES, np.uint8)
         tm = Timings()
-        self._ck(self.lib.fk_prove(self.handle, key.handle, _vp(a), _vp(b), _vp(c), C.c_uint64(a.shape[0]), _vp(z),
-                                   C.c_void_p(a_aux.ctypes.data), _vp(b_in), C.c_void_p(b_aux.ctypes.data),
+        self._ck(self.lib.fk_prove(self.handle, key.handle, _vp(a), _vp(b), _vp(c), a.shape[0], _vp(z),
+                                   _vp(a_aux), _vp(b_in), _vp(b_aux),
                                    _vp(r), _vp(s), _vp(out), C.byref(tm)))
         return (out, tm.as_dict()) if want_timings else out
 
@@ -1167,56 +1023,49 @@ class Context:
         a, b, c, z = _fr(a), _fr(b), _fr(c), _fr(z)
         a_aux, b_in, b_aux = _u8(a_aux), _u8(b_in), _u8(b_aux)
         out = np.zeros(FK_MSM_RESULT_BYTES, np.uint8)
-        self._ck(self.lib.fk_prove_msms(self.handle, key.handle, _vp(a), _vp(b), _vp(c), C.c_uint64(a.shape[0]), _vp(z),
-                                        C.c_void_p(a_aux.ctypes.data), _vp(b_in), C.c_void_p(b_aux.ctypes.data),
-                                        _vp(out), None))
+        self._ck(self.lib.fk_prove_msms(self.handle, key.handle, _vp(a), _vp(b), _vp(c), a.shape[0], _vp(z), _vp(a_aux), _vp(b_in), _vp(b_aux), _vp(out), None))
         return out
 
     def prove_msms_dev(self, key, d_a, d_b, d_c, n, d_z, d_a_aux, d_b_in, d_b_aux, want_timings=False):
         out = np.zeros(FK_MSM_RESULT_BYTES, np.uint8)
         tm = Timings()
-        self._ck(self.lib.fk_prove_msms_dev(self.handle, key.handle, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c),
-                                            C.c_uint64(n), C.c_void_p(d_z), C.c_void_p(d_a_aux), C.c_void_p(d_b_in),
-                                            C.c_void_p(d_b_aux), _vp(out), C.byref(tm)))
+        self._ck(self.lib.fk_prove_msms_dev(self.handle, key.handle, d_a, d_b, d_c, n, d_z, d_a_aux, d_b_in, d_b_aux, _vp(out), C.byref(tm)))
         return (out, tm.as_dict()) if want_timings else out
 
     def prove_msms_z_dev(self, key, d_z, d_a_aux, d_b_in, d_b_aux):
         """witness MSMs L, A, B1, B2 of this key's slices -> 384-byte record with H = identity"""
         out = np.zeros(FK_MSM_RESULT_BYTES, np.uint8)
-        self._ck(self.lib.fk_prove_msms_z_dev(self.handle, key.handle, C.c_void_p(d_z), C.c_void_p(d_a_aux), C.c_void_p(d_b_in),
-                                              C.c_void_p(d_b_aux), _vp(out), None))
+        self._ck(self.lib.fk_prove_msms_z_dev(self.handle, key.handle, d_z, d_a_aux, d_b_in, d_b_aux, _vp(out), None))
         return out
 
     def prove_msms_hz_dev(self, key, d_h_slice, d_z, d_a_aux, d_b_in, d_b_aux):
         """all five MSMs of this key's slices, H over the given block of quotient coefficients -> 384-byte record"""
         out = np.zeros(FK_MSM_RESULT_BYTES, np.uint8)
-        self._ck(self.lib.fk_prove_msms_hz_dev(self.handle, key.handle, C.c_void_p(d_h_slice), C.c_void_p(d_z), C.c_void_p(d_a_aux),
-                                               C.c_void_p(d_b_in), C.c_void_p(d_b_aux), _vp(out), None))
+        self._ck(self.lib.fk_prove_msms_hz_dev(self.handle, key.handle, d_h_slice, d_z, d_a_aux, d_b_in, d_b_aux, _vp(out), None))
         return out
 
     def prove_msms_hz_r1cs_dev(self, key, device_r1cs, d_h_slice, d_z):
         """all five MSMs of this key's slices for a resident constraint system -> 384-byte record"""
         out = np.zeros(FK_MSM_RESULT_BYTES, np.uint8)
-        self._ck(self.lib.fk_prove_msms_hz_r1cs_dev(self.handle, key.handle, device_r1cs.handle, C.c_void_p(d_h_slice), C.c_void_p(d_z), _vp(out)))
+        self._ck(self.lib.fk_prove_msms_hz_r1cs_dev(self.handle, key.handle, device_r1cs.handle, d_h_slice, d_z, _vp(out)))
         return out
 
     def prove_msms_z_begin_dev(self, key, d_z, d_a_aux, d_b_in, d_b_aux):
         """queue L, A, B1, B2 on the MSM streams and return; pair with prove_msms_finish_dev"""
-        self._ck(self.lib.fk_prove_msms_z_begin_dev(self.handle, key.handle, C.c_void_p(d_z), C.c_void_p(d_a_aux), C.c_void_p(d_b_in),
-                                                    C.c_void_p(d_b_aux)))
+        self._ck(self.lib.fk_prove_msms_z_begin_dev(self.handle, key.handle, d_z, d_a_aux, d_b_in, d_b_aux))
 
     def prove_msms_z_begin_r1cs_dev(self, key, device_r1cs, d_z):
         """the same for a resident constraint system (index-list gathers instead of the density compaction)"""
-        self._ck(self.lib.fk_prove_msms_z_begin_r1cs_dev(self.handle, key.handle, device_r1cs.handle, C.c_void_p(d_z)))
+        self._ck(self.lib.fk_prove_msms_z_begin_r1cs_dev(self.handle, key.handle, device_r1cs.handle, d_z))
 
     def prove_msms_finish_dev(self, key, d_h_slice):
         out = np.zeros(FK_MSM_RESULT_BYTES, np.uint8)
-        self._ck(self.lib.fk_prove_msms_finish_dev(self.handle, key.handle, C.c_void_p(d_h_slice), _vp(out)))
+        self._ck(self.lib.fk_prove_msms_finish_dev(self.handle, key.handle, d_h_slice, _vp(out)))
         return out
 
     def prove_msm_h_dev(self, key, d_h_slice):
         out = np.zeros(64, np.uint8)
-        self._ck(self.lib.fk_prove_msm_h_dev(self.handle, key.handle, C.c_void_p(d_h_slice), _vp(out)))
+        self._ck(self.lib.fk_prove_msm_h_dev(self.handle, key.handle, d_h_slice, _vp(out)))
         return out
 
     ARRAYS = {'h': 0, 'l': 1, 'a': 2, 'b_g1': 3, 'b_g2': 4}
@@ -1225,31 +1074,22 @@ class Context:
         """fk_prove_msm_array_dev: ONE multiplication over the key's resident array `which` ('h', 'l', 'a', 'b_g1', 'b_g2'; with its
         fixed-base levels when held), one scalar per point of the key's slice; raw affine result (64 B, 128 B for 'b_g2')"""
         out = np.zeros(128 if which == 'b_g2' else 64, np.uint8)
-        self._ck(self.lib.fk_prove_msm_array_dev(self.handle, key.handle, C.c_int(self.ARRAYS[which]), C.c_void_p(d_scalars), _vp(out)))
+        self._ck(self.lib.fk_prove_msm_array_dev(self.handle, key.handle, self.ARRAYS[which], d_scalars, _vp(out)))
         return out
 
     def prove_dev(self, key, d_a, d_b, d_c, n, d_z, d_a_aux, d_b_in, d_b_aux, r, s, want_timings=False):
         out = np.zeros(FK_PROOF_BYTES, np.uint8)
         tm = Timings()
         r, s = _fr(r, 1), _fr(s, 1)
-        self._ck(self.lib.fk_prove_dev(self.handle, key.handle, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c),
-                                       C.c_uint64(n), C.c_void_p(d_z), C.c_void_p(d_a_aux), C.c_void_p(d_b_in),
-                                       C.c_void_p(d_b_aux), _vp(r), _vp(s), _vp(out), C.byref(tm)))
+        self._ck(self.lib.fk_prove_dev(self.handle, key.handle, d_a, d_b, d_c, n, d_z, d_a_aux, d_b_in, d_b_aux, _vp(r), _vp(s), _vp(out), C.byref(tm)))
         return (out, tm.as_dict()) if want_timings else out
 
     def load_key_bellman(self, data, shard_index=0, shard_count=1, z_frac=Z_EQUAL_SPLIT, flags=FK_KEY_CHECKED):
         """fk_key_load_bellman: `data` = bytes of bellman's Parameters::write; flags = FK_KEY_CHECKED | FK_KEY_NO_INFINITY (the
         `checked` / `disallow_points_at_infinity` arguments of Parameters::read, mod.rs:159).  Returns (DeviceKey, gamma_g2, ic)."""
         buf = _bytes_view(data)      # (no copy of a multi-GB array)
-        h = C.c_void_p()
-        gamma = np.zeros(128, np.uint8)
-        n_ic = C.c_uint32()
-        cap = 1 << 16
-        ic = np.zeros((cap, 64), np.uint8)
-        self._ck(self.lib.fk_key_load_bellman(self.handle, _vp(buf), C.c_size_t(buf.size), C.c_uint32(flags), C.c_uint32(shard_index), C.c_uint32(shard_count),
-                                              C.c_double(z_frac[0]), C.c_double(z_frac[1]), C.byref(h), _vp(gamma), _vp(ic), C.c_uint32(cap),
-                                              C.byref(n_ic)))
-        return DeviceKey(self, h, shard_index, shard_count), gamma, ic[:min(n_ic.value, cap)].copy()
+        h, gamma, ic = _load_bellman(self._ck, self.lib.fk_key_load_bellman, self.handle, _vp(buf), buf.size, flags, shard_index, shard_count, z_frac[0], z_frac[1])
+        return DeviceKey(self, h, shard_index, shard_count), gamma, ic
 
     def write_key_bellman(self, key, vk, out=None, size_only=False):
         """fk_key_write_bellman: bellman `Parameters::write` bytes of a whole resident key (GPU conversion); vk: the dict fk_setup* /
@@ -1258,13 +1098,13 @@ class Context:
         gamma = np.ascontiguousarray(vk['gamma_g2'], np.uint8).reshape(-1)
         ic = np.ascontiguousarray(vk['ic'], np.uint8).reshape(-1, 64)
         need = C.c_size_t()
-        self._ck(self.lib.fk_key_write_bellman(self.handle, key.handle, _vp(gamma), _vp(ic), C.c_uint32(ic.shape[0]), None, C.c_size_t(0), C.byref(need)))
+        self._ck(self.lib.fk_key_write_bellman(self.handle, key.handle, _vp(gamma), _vp(ic), ic.shape[0], None, 0, C.byref(need)))
         if size_only:
             return need.value
         if out is None:
             out = np.empty(need.value, np.uint8)
         assert out.dtype == np.uint8 and out.flags['C_CONTIGUOUS'] and out.nbytes >= need.value
-        self._ck(self.lib.fk_key_write_bellman(self.handle, key.handle, _vp(gamma), _vp(ic), C.c_uint32(ic.shape[0]), _vp(out), C.c_size_t(out.nbytes), C.byref(need)))
+        self._ck(self.lib.fk_key_write_bellman(self.handle, key.handle, _vp(gamma), _vp(ic), ic.shape[0], _vp(out), out.nbytes, C.byref(need)))
         return out[:need.value]
 
     def setup(self, r1cs, tau, alpha, beta, gamma, delta, shard_index=0, shard_count=1, z_frac=Z_EQUAL_SPLIT, copies=None):
@@ -1274,18 +1114,14 @@ class Context:
         h = C.c_void_p()
         vk = np.zeros(6 * 128, np.uint8)
         tau, alpha, beta, gamma, delta = _fr(tau, 1), _fr(alpha, 1), _fr(beta, 1), _fr(gamma, 1), _fr(delta, 1)
-        tail = (_vp(tau), _vp(alpha), _vp(beta), _vp(gamma), _vp(delta), C.c_uint32(shard_index),
-                C.c_uint32(shard_count), C.c_double(z_frac[0]), C.c_double(z_frac[1]), C.byref(h), _vp(vk))
+        tail = (_vp(tau), _vp(alpha), _vp(beta), _vp(gamma), _vp(delta), shard_index, shard_count, z_frac[0], z_frac[1], C.byref(h), _vp(vk))
         if copies is None:
             ic = np.zeros((r1cs.num_input, 64), np.uint8)
             self._ck(self.lib.fk_setup(self.handle, C.byref(r1cs.struct), *tail, _vp(ic)))
         else:
             ic = np.zeros((1 + int(copies) * (r1cs.num_input - 1), 64), np.uint8)
-            self._ck(self.lib.fk_setup_tiled(self.handle, C.byref(r1cs.struct), C.c_uint32(int(copies)), *tail, _vp(ic)))
-        names = (('alpha_g1', 64), ('beta_g1', 64), ('beta_g2', 128), ('gamma_g2', 128), ('delta_g1', 64), ('delta_g2', 128))
-        out = {n: vk[i * 128:i * 128 + w].copy() for i, (n, w) in enumerate(names)}
-        out['ic'] = ic
-        return DeviceKey(self, h, shard_index, shard_count), out
+            self._ck(self.lib.fk_setup_tiled(self.handle, C.byref(r1cs.struct), int(copies), *tail, _vp(ic)))
+        return DeviceKey(self, h, shard_index, shard_count), _vk_dict(vk, ic)
 
     # ---- device-resident constraint system: only the witness crosses the boundary
     def load_r1cs(self, r1cs, copies=None):
@@ -1294,7 +1130,7 @@ class Context:
         if copies is None:
             self._ck(self.lib.fk_r1cs_load(self.handle, C.byref(r1cs.struct), C.byref(h)))
         else:
-            self._ck(self.lib.fk_r1cs_load_tiled(self.handle, C.byref(r1cs.struct), C.c_uint32(int(copies)), C.byref(h)))
+            self._ck(self.lib.fk_r1cs_load_tiled(self.handle, C.byref(r1cs.struct), int(copies), C.byref(h)))
         return DeviceR1cs(self, h)
 
     def load_r1cs_coded(self, num_input, num_aux, mats, table):
@@ -1312,16 +1148,15 @@ class Context:
             cidx.append(ci)
         table = _fr(table)
         h = C.c_void_p()
-        self._ck(self.lib.fk_r1cs_load_coded(self.handle, C.byref(st), _vp(cidx[0]), _vp(cidx[1]), _vp(cidx[2]), _vp(table), C.c_uint64(len(table)), C.byref(h)))
+        self._ck(self.lib.fk_r1cs_load_coded(self.handle, C.byref(st), _vp(cidx[0]), _vp(cidx[1]), _vp(cidx[2]), _vp(table), len(table), C.byref(h)))
         return DeviceR1cs(self, h)
 
     def r1cs_eval_dev(self, dr, d_z, d_a, d_b, d_c):
-        self._ck(self.lib.fk_r1cs_eval_dev(self.handle, dr.handle, C.c_void_p(d_z), C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c)))
+        self._ck(self.lib.fk_r1cs_eval_dev(self.handle, dr.handle, d_z, d_a, d_b, d_c))
 
     def r1cs_eval_slice_dev(self, dr, d_z, log_m, rank, log_w, d_a, d_b, d_c):
         """fk_r1cs_eval_slice_dev: the cyclic row slice of rank `rank` of 2^log_w (2^(log_m - log_w) elements per array)"""
-        self._ck(self.lib.fk_r1cs_eval_slice_dev(self.handle, dr.handle, C.c_void_p(d_z), C.c_uint32(log_m), C.c_uint32(rank), C.c_uint32(log_w),
-                                                 C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c)))
+        self._ck(self.lib.fk_r1cs_eval_slice_dev(self.handle, dr.handle, d_z, log_m, rank, log_w, d_a, d_b, d_c))
 
     def prove_witness(self, key, dr, z, r, s, want_timings=False):
         """fk_prove_r1cs: z (host, (num_input+num_aux, 4) uint64 Montgomery) -> 256-byte proof."""
@@ -1336,7 +1171,7 @@ class Context:
         out = np.zeros(FK_PROOF_BYTES, np.uint8)
         tm = Timings()
         r, s = _fr(r, 1), _fr(s, 1)
-        self._ck(self.lib.fk_prove_r1cs_dev(self.handle, key.handle, dr.handle, C.c_void_p(d_z), _vp(r), _vp(s), _vp(out), C.byref(tm)))
+        self._ck(self.lib.fk_prove_r1cs_dev(self.handle, key.handle, dr.handle, d_z, _vp(r), _vp(s), _vp(out), C.byref(tm)))
         return (out, tm.as_dict()) if want_timings else out
 
     def prove_assemble(self, key, parts, r, s):
@@ -1350,15 +1185,15 @@ class Context:
         out = {}
         for which, name in ((0, 'acc_g1'), (1, 'acc_g2'), (2, 'ntt')):
             ms, n, u = C.c_double(), C.c_uint64(), C.c_uint64()
-            self._ck(self.lib.fk_stats_get(self.handle, C.c_int(which), C.byref(ms), C.byref(n), C.byref(u)))
+            self._ck(self.lib.fk_stats_get(self.handle, which, C.byref(ms), C.byref(n), C.byref(u)))
             out[name] = dict(ms=ms.value, launches=n.value, units=u.value)
         for which, name in ((3, 'acc_g1'), (4, 'acc_g2')):     # the same kernels, counted in mixed point additions
             u = C.c_uint64()
-            self._ck(self.lib.fk_stats_get(self.handle, C.c_int(which), None, None, C.byref(u)))
+            self._ck(self.lib.fk_stats_get(self.handle, which, None, None, C.byref(u)))
             out[name]['adds'] = u.value
         for which, name in ((5, 'acc_g1'), (6, 'acc_g2')):     # union of the launches' intervals (launches side by side)
             ms = C.c_double()
-            self._ck(self.lib.fk_stats_get(self.handle, C.c_int(which), C.byref(ms), None, None))
+            self._ck(self.lib.fk_stats_get(self.handle, which, C.byref(ms), None, None))
             out[name]['union_ms'] = ms.value
         return out
 
@@ -1369,7 +1204,7 @@ class Context:
         return dict(mad_lane_ops_per_s=out[0], modmul_per_s=out[1])
 
     def dev_copy(self, dst, src, nbytes):
-        self._ck(self.lib.fk_dev_copy(self.handle, C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes)))
+        self._ck(self.lib.fk_dev_copy(self.handle, dst, src, nbytes))
 
     # ---- Poseidon (native/poseidon.rs): inputs as canonical ints give ints back, Montgomery limb arrays (dtype uint64) give limbs back
     def poseidon(self, params, inputs):
@@ -1384,11 +1219,11 @@ class Context:
                 raise ValueError('poseidon: every row takes the same number of inputs')
         a = _fr_rows(inputs, n * k)
         out = np.zeros((n, 4), np.uint64)
-        self._ck(self.lib.fk_poseidon_hash_batch(self.handle, params.handle, _vp(a), C.c_uint32(k), C.c_size_t(n), _vp(out)))
+        self._ck(self.lib.fk_poseidon_hash_batch(self.handle, params.handle, _vp(a), k, n, _vp(out)))
         return out if as_limbs else _fr_ints(out)
 
     def poseidon_dev(self, params, d_inputs, n_inputs, n, d_out):
-        self._ck(self.lib.fk_poseidon_hash_batch_dev(self.handle, params.handle, C.c_void_p(d_inputs), C.c_uint32(n_inputs), C.c_size_t(n), C.c_void_p(d_out)))
+        self._ck(self.lib.fk_poseidon_hash_batch_dev(self.handle, params.handle, d_inputs, n_inputs, n, d_out))
 
     def poseidon_sponge(self, params, messages):
         """poseidon_sponge(messages[i], params) for n messages of one length: (n, len, 4) limbs or a list of n tuples of ints"""
@@ -1402,11 +1237,11 @@ class Context:
                 raise ValueError('poseidon_sponge: one call takes messages of one length')
         a = _fr_rows(messages, n * ln) if n * ln else None
         out = np.zeros((n, 4), np.uint64)
-        self._ck(self.lib.fk_poseidon_sponge_batch(self.handle, params.handle, _vp(a), C.c_uint64(ln), C.c_size_t(n), _vp(out)))
+        self._ck(self.lib.fk_poseidon_sponge_batch(self.handle, params.handle, _vp(a), ln, n, _vp(out)))
         return out if as_limbs else _fr_ints(out)
 
     def merkle_tree_dev(self, params, d_leaves, n_leaves, d_nodes):
-        self._ck(self.lib.fk_poseidon_merkle_tree_dev(self.handle, params.handle, C.c_void_p(d_leaves), C.c_uint64(n_leaves), C.c_void_p(d_nodes)))
+        self._ck(self.lib.fk_poseidon_merkle_tree_dev(self.handle, params.handle, d_leaves, n_leaves, d_nodes))
 
     def merkle_tree(self, params, leaves):
         """the whole tree over `leaves` (zero-padded to a power of two), kept in device memory -> MerkleTree"""
@@ -1429,7 +1264,7 @@ class Context:
         as_limbs = isinstance(leaves, np.ndarray) and leaves.dtype == np.uint64
         a = _fr_rows(leaves)
         out = np.zeros((1, 4), np.uint64)
-        self._ck(self.lib.fk_poseidon_merkle_root(self.handle, params.handle, _vp(a), C.c_uint64(a.shape[0]), _vp(out)))
+        self._ck(self.lib.fk_poseidon_merkle_root(self.handle, params.handle, _vp(a), a.shape[0], _vp(out)))
         return out[0] if as_limbs else _fr_ints(out)[0]
 
     def merkle_proof_roots(self, params, leaves, siblings, indices, depth):
@@ -1442,12 +1277,11 @@ class Context:
         if ia.shape[0] != n:
             raise ValueError('merkle_proof_roots: one index per leaf')
         out = np.zeros((n, 4), np.uint64)
-        self._ck(self.lib.fk_poseidon_merkle_proof_roots(self.handle, params.handle, _vp(la), _vp(sa), _vp(ia), C.c_uint32(depth), C.c_size_t(n), _vp(out)))
+        self._ck(self.lib.fk_poseidon_merkle_proof_roots(self.handle, params.handle, _vp(la), _vp(sa), _vp(ia), depth, n, _vp(out)))
         return out if as_limbs else _fr_ints(out)
 
     def merkle_proof_roots_dev(self, params, d_leaves, d_siblings, d_indices, depth, n, d_out):
-        self._ck(self.lib.fk_poseidon_merkle_proof_roots_dev(self.handle, params.handle, C.c_void_p(d_leaves), C.c_void_p(d_siblings), C.c_void_p(d_indices),
-                                                             C.c_uint32(depth), C.c_size_t(n), C.c_void_p(d_out)))
+        self._ck(self.lib.fk_poseidon_merkle_proof_roots_dev(self.handle, params.handle, d_leaves, d_siblings, d_indices, depth, n, d_out))
 
     # ---- JubJub / EdDSA-Poseidon (native/ecc.rs, native/eddsaposeidon.rs).  Fr elements: canonical ints or Montgomery limb arrays; Fs
     # elements (scalars, s, sk, rho): ints or canonical limb arrays.  Ints in give ints out, limb arrays in give limb arrays out.
@@ -1458,7 +1292,7 @@ class Context:
         n = ka.shape[0]
         pa = None if points is None else _fr_rows(points if _is_limbs(points) else [c for pt in points for c in pt], 2 * n)
         out = np.zeros((n, 2, 4), np.uint64)
-        self._ck(self.lib.fk_jubjub_mul_batch(self.handle, _vp(pa), _vp(ka), C.c_size_t(n), _vp(out)))
+        self._ck(self.lib.fk_jubjub_mul_batch(self.handle, _vp(pa), _vp(ka), n, _vp(out)))
         if as_limbs:
             return out
         v = _fr_ints(out)
@@ -1470,7 +1304,7 @@ class Context:
         xa = _fr_rows(xs)
         n = xa.shape[0]
         y, ok = np.zeros((n, 4), np.uint64), np.zeros(n, np.uint8)
-        self._ck(self.lib.fk_jubjub_decompress_batch(self.handle, _vp(xa), C.c_size_t(n), _vp(y), _vp(ok)))
+        self._ck(self.lib.fk_jubjub_decompress_batch(self.handle, _vp(xa), n, _vp(y), _vp(ok)))
         if as_limbs:
             return y, ok
         return [v if f else None for v, f in zip(_fr_ints(y), ok)]
@@ -1483,7 +1317,7 @@ class Context:
         ma = _fr_rows(ms, n)
         ra = None if rhos is None else _u256_rows(rhos, n)
         s, r_x, a_x = (np.zeros((n, 4), np.uint64) for _ in range(3))
-        self._ck(self.lib.fk_eddsa_sign_batch(self.handle, params.handle, _vp(ka), _vp(ma), _vp(ra), C.c_size_t(n), _vp(s), _vp(r_x), _vp(a_x)))
+        self._ck(self.lib.fk_eddsa_sign_batch(self.handle, params.handle, _vp(ka), _vp(ma), _vp(ra), n, _vp(s), _vp(r_x), _vp(a_x)))
         if as_limbs:
             return s, r_x, a_x
         return _u256_ints(s), _fr_ints(r_x), _fr_ints(a_x)
@@ -1494,33 +1328,24 @@ class Context:
         n = sa.shape[0]
         ra, aa, ma = _fr_rows(r, n), _fr_rows(a, n), _fr_rows(m, n)
         acc = np.zeros(n, np.uint8)
-        self._ck(self.lib.fk_eddsa_verify_batch(self.handle, params.handle, _vp(sa), _vp(ra), _vp(aa), _vp(ma), C.c_size_t(n), _vp(acc)))
+        self._ck(self.lib.fk_eddsa_verify_batch(self.handle, params.handle, _vp(sa), _vp(ra), _vp(aa), _vp(ma), n, _vp(acc)))
         return [bool(v) for v in acc]
 
     def eddsa_verify_dev(self, params, d_s, d_r, d_a, d_m, n, d_accept):
-        self._ck(self.lib.fk_eddsa_verify_batch_dev(self.handle, params.handle, C.c_void_p(d_s), C.c_void_p(d_r), C.c_void_p(d_a), C.c_void_p(d_m),
-                                                    C.c_size_t(n), C.c_void_p(d_accept)))
+        self._ck(self.lib.fk_eddsa_verify_batch_dev(self.handle, params.handle, d_s, d_r, d_a, d_m, n, d_accept))
 
 
-class _MultiHandle:
+class _MultiHandle(_Handle):
     """a key / constraint system loaded through a MultiContext (one shard / replica per GPU)"""
 
     def __init__(self, multi, handle, free_fn):
         self.multi, self.handle, self._free = multi, handle, free_fn
 
-    def free(self):
-        if self.handle is not None:
-            self._free(self.multi.handle or None, self.handle)      # a closed MultiContext: the device memory is released all the same
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, h):
+        self._free(self.multi.handle or None, h)      # a closed MultiContext: the device memory is released all the same
 
 
-class MultiContext:
+class MultiContext(_Handle):
     """N GPUs of one node behind ONE call (fk_init_devices / fk_multi_*, csrc/multi.hip): one process, a library context and a
     worker thread per GPU, exchanges inside the library.  `device_ids` may repeat (ranks sharing a GPU: one-GPU test boxes).
     The reference's `prove` (prover.rs:63-90) is one call; so is `prove_witness` here, whatever N is."""
@@ -1529,9 +1354,8 @@ class MultiContext:
         self.lib = load_library()
         ids = (C.c_int * len(device_ids))(*[int(d) for d in device_ids])
         h = C.c_void_p()
-        rc = self.lib.fk_init_devices(C.c_int(len(device_ids)), ids, C.byref(h))
-        if rc != 0:
-            raise FkError(rc, 'fk_init_devices(%s) failed -- no usable MI355X/HIP device; there is no CPU fallback' % list(device_ids))
+        _check(self.lib.fk_init_devices(len(device_ids), ids, C.byref(h)),
+               'fk_init_devices(%s) failed -- no usable MI355X/HIP device; there is no CPU fallback' % list(device_ids))
         self.handle = h
         self.device_ids = list(device_ids)
         self._tickets = {}
@@ -1568,29 +1392,22 @@ class MultiContext:
         gb = (C.c_double * (n * n))()
         st = (C.c_int32 * (n * n))()
         he = C.c_int(0)
-        rc = self.lib.fk_multi_preflight(self.handle, C.c_size_t(int(nbytes)), gb, st, C.byref(he))
+        rc = self.lib.fk_multi_preflight(self.handle, int(nbytes), gb, st, C.byref(he))
         return dict(ok=rc == 0, rc=int(rc), bytes=int(nbytes), gbps=[[round(float(gb[i * n + j]), 2) for j in range(n)] for i in range(n)],
                     status=[[int(st[i * n + j]) for j in range(n)] for i in range(n)], host_events=bool(he.value), note=self.note())
 
-    def close(self):
-        if getattr(self, 'handle', None):
-            self.lib.fk_multi_free(self.handle)
-            self.handle = None
+    def _release(self, h):
+        self.lib.fk_multi_free(h)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def close(self):
+        self.free()
 
     def _ck(self, rc):
-        if rc != 0:
-            msg = self.lib.fk_multi_last_error(self.handle)
-            raise FkError(rc, msg.decode() if msg else '')
+        _check(rc, '', self.lib.fk_multi_last_error, self.handle)
 
     def ctx(self, rank):
         """rank's single-GPU Context (borrowed: statistics, calibration, pinned host buffers)"""
-        p = self.lib.fk_multi_ctx(self.handle, C.c_int(rank))
+        p = self.lib.fk_multi_ctx(self.handle, rank)
         if not p:
             raise IndexError(rank)
         return Context(self.device_ids[rank], _borrowed=p)
@@ -1612,14 +1429,8 @@ class MultiContext:
 
     def load_key_bellman(self, data, flags=FK_KEY_CHECKED):
         buf = _bytes_view(data)      # (no copy of a multi-GB array)
-        h = C.c_void_p()
-        gamma = np.zeros(128, np.uint8)
-        n_ic = C.c_uint32()
-        cap = 1 << 16
-        ic = np.zeros((cap, 64), np.uint8)
-        self._ck(self.lib.fk_multi_key_load_bellman(self.handle, _vp(buf), C.c_size_t(buf.size), C.c_uint32(flags), C.byref(h), _vp(gamma), _vp(ic),
-                                                    C.c_uint32(cap), C.byref(n_ic)))
-        return _MultiHandle(self, h, self.lib.fk_multi_key_free), gamma, ic[:min(n_ic.value, cap)].copy()
+        h, gamma, ic = _load_bellman(self._ck, self.lib.fk_multi_key_load_bellman, self.handle, _vp(buf), buf.size, flags)
+        return _MultiHandle(self, h, self.lib.fk_multi_key_free), gamma, ic
 
     def setup(self, r1cs, tau, alpha, beta, gamma, delta, copies=None):
         """fk_multi_setup / fk_multi_setup_tiled: rank g derives only shard g.  Returns (key, vk dict) like Context.setup."""
@@ -1632,24 +1443,19 @@ class MultiContext:
             self._ck(self.lib.fk_multi_setup(self.handle, C.byref(r1cs.struct), *tox, C.byref(h), _vp(vk), _vp(ic)))
         else:
             ic = np.zeros((1 + int(copies) * (r1cs.num_input - 1), 64), np.uint8)
-            self._ck(self.lib.fk_multi_setup_tiled(self.handle, C.byref(r1cs.struct), C.c_uint32(int(copies)), *tox, C.byref(h), _vp(vk), _vp(ic)))
-        names = (('alpha_g1', 64), ('beta_g1', 64), ('beta_g2', 128), ('gamma_g2', 128), ('delta_g1', 64), ('delta_g2', 128))
-        out = {n: vk[i * 128:i * 128 + w].copy() for i, (n, w) in enumerate(names)}
-        out['ic'] = ic
-        return _MultiHandle(self, h, self.lib.fk_multi_key_free), out
+            self._ck(self.lib.fk_multi_setup_tiled(self.handle, C.byref(r1cs.struct), int(copies), *tox, C.byref(h), _vp(vk), _vp(ic)))
+        return _MultiHandle(self, h, self.lib.fk_multi_key_free), _vk_dict(vk, ic)
 
     def key_shard(self, key, rank):
         """rank's shard as a (borrowed) DeviceKey: counts(), shard_info(), precomputed()"""
-        dk = DeviceKey(self.ctx(rank), C.c_void_p(self.lib.fk_multi_key_shard(key.handle, C.c_int(rank))), rank, self.size)
-        dk.free = lambda: None
-        return dk
+        return DeviceKey(self.ctx(rank), self.lib.fk_multi_key_shard(key.handle, rank), rank, self.size, borrowed=True)
 
     def load_r1cs(self, r1cs, copies=None):
         h = C.c_void_p()
         if copies is None:
             self._ck(self.lib.fk_multi_r1cs_load(self.handle, C.byref(r1cs.struct), C.byref(h)))
         else:
-            self._ck(self.lib.fk_multi_r1cs_load_tiled(self.handle, C.byref(r1cs.struct), C.c_uint32(int(copies)), C.byref(h)))
+            self._ck(self.lib.fk_multi_r1cs_load_tiled(self.handle, C.byref(r1cs.struct), int(copies), C.byref(h)))
         return _MultiHandle(self, h, self.lib.fk_multi_r1cs_free)
 
     def load_gates(self, gates):
@@ -1658,9 +1464,7 @@ class MultiContext:
         return _MultiHandle(self, h, self.lib.fk_multi_r1cs_free)
 
     def r1cs_replica(self, dr, rank):
-        d = DeviceR1cs(self.ctx(rank), C.c_void_p(self.lib.fk_multi_r1cs_replica(dr.handle, C.c_int(rank))))
-        d.free = lambda: None
-        return d
+        return DeviceR1cs(self.ctx(rank), self.lib.fk_multi_r1cs_replica(dr.handle, rank), borrowed=True)
 
     def prove_witness(self, key, dr, z, r, s, want_timings=False):
         """fk_multi_prove_r1cs: z (host, (num_input + num_aux, 4) uint64 Montgomery) -> 256-byte proof, on all GPUs"""
@@ -1684,7 +1488,7 @@ class MultiContext:
         out = np.zeros(FK_PROOF_BYTES, np.uint8)
         tm = Timings()
         try:
-            self._ck(self.lib.fk_multi_prove_r1cs_wait(self.handle, C.c_int(ticket), _vp(out), C.byref(tm)))
+            self._ck(self.lib.fk_multi_prove_r1cs_wait(self.handle, ticket, _vp(out), C.byref(tm)))
         finally:
             self._tickets.pop(ticket, None)
         return (out, tm.as_dict()) if want_timings else out
@@ -1700,11 +1504,9 @@ def synthesize(r1cs, z, ctx=None):
     a_aux = np.zeros(max(r1cs.num_aux, 1), np.uint8)[:r1cs.num_aux]
     b_in = np.zeros(r1cs.num_input, np.uint8)
     b_aux = np.zeros(max(r1cs.num_aux, 1), np.uint8)[:r1cs.num_aux]
-    rc = lib.fk_synthesize(ctx.handle if ctx else None, C.byref(r1cs.struct), _vp(z), _vp(a), _vp(b), _vp(c),
-                           C.c_void_p(a_aux.ctypes.data), _vp(b_in), C.c_void_p(b_aux.ctypes.data))
-    if rc != 0:
-        msg = lib.fk_last_error(ctx.handle) if ctx else b''
-        raise FkError(rc, msg.decode() if msg else '')
+    ch = ctx.handle if ctx else None
+    rc = lib.fk_synthesize(ch, C.byref(r1cs.struct), _vp(z), _vp(a), _vp(b), _vp(c), _vp(a_aux), _vp(b_in), _vp(b_aux))
+    _check(rc, '', ctx and lib.fk_last_error, ch)
     return a, b, c, a_aux, b_in, b_aux
 
 
@@ -1714,27 +1516,22 @@ def assemble(key_handle, parts, r, s, ctx=None):
     parts = np.ascontiguousarray(parts, np.uint8).reshape(-1, FK_MSM_RESULT_BYTES)
     out = np.zeros(FK_PROOF_BYTES, np.uint8)
     r, s = _fr(r, 1), _fr(s, 1)
-    rc = lib.fk_prove_assemble(ctx.handle if ctx else None, key_handle, _vp(parts), C.c_uint32(parts.shape[0]),
-                               _vp(r), _vp(s), _vp(out))
-    if rc != 0:
-        msg = lib.fk_last_error(ctx.handle) if ctx else b''
-        raise FkError(rc, msg.decode() if msg else '')
+    ch = ctx.handle if ctx else None
+    _check(lib.fk_prove_assemble(ch, key_handle, _vp(parts), parts.shape[0], _vp(r), _vp(s), _vp(out)), '', ctx and lib.fk_last_error, ch)
     return out
 
 
 def msm_plan(n, window_bits=0, merged=False):
     """fk_msm_plan (host only, no GPU): dict of the window plan for n points and of the limits it is sized against"""
     info = MsmPlanInfo()
-    rc = load_library().fk_msm_plan(C.c_size_t(n), C.c_uint(window_bits), C.c_int(int(merged)), C.byref(info))
-    if rc != 0:
-        raise FkError(rc, 'fk_msm_plan')
+    _check(load_library().fk_msm_plan(n, window_bits, int(merged), C.byref(info)), 'fk_msm_plan')
     return {f: int(getattr(info, f)) for f, _ in MsmPlanInfo._fields_}
 
 
 def shard_range(n, index, count):
     lib = load_library()
     lo, hi = C.c_uint64(), C.c_uint64()
-    lib.fk_shard_range(C.c_uint64(n), C.c_uint32(index), C.c_uint32(count), C.byref(lo), C.byref(hi))
+    lib.fk_shard_range(n, index, count, C.byref(lo), C.byref(hi))
     return lo.value, hi.value
 
 
@@ -1744,9 +1541,9 @@ def work_shard_ranges(n_l, n_a, n_b, index, count, q0_domain=None):
     lib = load_library()
     out = (C.c_uint64 * 8)()
     if q0_domain is None:
-        lib.fk_work_shard_ranges(C.c_uint64(n_l), C.c_uint64(n_a), C.c_uint64(n_b), C.c_uint32(index), C.c_uint32(count), out)
+        lib.fk_work_shard_ranges(n_l, n_a, n_b, index, count, out)
     else:
-        lib.fk_work_shard_ranges_q0(C.c_uint64(n_l), C.c_uint64(n_a), C.c_uint64(n_b), C.c_uint64(q0_domain), C.c_uint32(index), C.c_uint32(count), out)
+        lib.fk_work_shard_ranges_q0(n_l, n_a, n_b, q0_domain, index, count, out)
     v = list(out)
     return dict(l=(v[0], v[1]), a=(v[2], v[3]), b=(v[4], v[5]), b_g2=(v[6], v[7]))
 
@@ -1755,7 +1552,7 @@ def h_shard_range(n_h, index, count):
     """[lo, hi) of the h bases shard `index` holds: blocks of the evaluation domain (fk_h_shard_range)"""
     lib = load_library()
     lo, hi = C.c_uint64(), C.c_uint64()
-    lib.fk_h_shard_range(C.c_uint64(n_h), C.c_uint32(index), C.c_uint32(count), C.byref(lo), C.byref(hi))
+    lib.fk_h_shard_range(n_h, index, count, C.byref(lo), C.byref(hi))
     return lo.value, hi.value
 
 
@@ -1783,10 +1580,8 @@ def verify(vk_borsh, inputs, proof, ctx=None):
     assert pr.size == FK_PROOF_BYTES
     inp = np.ascontiguousarray(inputs, np.uint64).reshape(-1, 4)
     ok = C.c_int(0)
-    rc = lib.fk_verify(ctx.handle if ctx else None, _vp(vkb), C.c_size_t(vkb.size), _vp(inp), C.c_uint32(inp.shape[0]), _vp(pr), C.byref(ok))
-    if rc != 0:
-        msg = lib.fk_last_error(ctx.handle) if ctx else b''
-        raise FkError(rc, msg.decode() if msg else 'fk_verify')
+    ch = ctx.handle if ctx else None
+    _check(lib.fk_verify(ch, _vp(vkb), vkb.size, _vp(inp), inp.shape[0], _vp(pr), C.byref(ok)), 'fk_verify', ctx and lib.fk_last_error, ch)
     return bool(ok.value)
 
 
@@ -1799,8 +1594,7 @@ def verify_batch(ctx, vk_borsh, inputs, proofs):
     inp = np.ascontiguousarray(inputs, np.uint64)
     inp = inp.reshape(pr.shape[0], -1, 4) if inp.size else np.zeros((pr.shape[0], 0, 4), np.uint64)     # a key without public inputs
     out = np.zeros(pr.shape[0], np.uint8)
-    ctx._ck(ctx.lib.fk_verify_batch_dev(ctx.handle, _vp(vkb), C.c_size_t(vkb.size), _vp(inp), C.c_uint32(inp.shape[1]), _vp(pr),
-                                        C.c_uint32(pr.shape[0]), _vp(out)))
+    ctx._ck(ctx.lib.fk_verify_batch_dev(ctx.handle, _vp(vkb), vkb.size, _vp(inp), inp.shape[1], _vp(pr), pr.shape[0], _vp(out)))
     return out.astype(bool)
 
 

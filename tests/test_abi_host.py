@@ -301,3 +301,80 @@ def test_header_is_plain_c():
     import re
     code = re.sub(r'/\*.*?\*/', '', open(hdr).read(), flags=re.S)          # declarations only (a comment says "no torch types")
     assert 'torch' not in code.lower() and 'std::' not in code and 'template' not in code and 'at::' not in code
+
+
+def test_native_handles_are_released_once_and_borrowed_ones_never():
+    """api._Handle, the one owner of a native handle, against fake release functions (no library involved): free() releases once however
+    often free() / __del__ run, a borrowed handle is never released, a half-constructed object can be collected, and the two rules the
+    subclasses add hold -- Gates clears its handle BEFORE the release (load_parameters frees it on a background thread), a _MultiHandle
+    passes its parent's handle as None once the parent is closed."""
+    from types import SimpleNamespace
+    from fawkes_crypto_amd import api
+    log = []
+
+    class Owner(api._Handle):
+        def __init__(self, handle, borrowed=False, fail=False):
+            if fail:
+                raise RuntimeError('before handle is set')
+            self.handle, self.borrowed = handle, borrowed
+
+        def _release(self, h):
+            log.append((h, self.handle))
+
+    o = Owner(7)
+    o.free(); o.free(); o.__del__(); o.__del__()
+    assert log == [(7, None)] and o.handle is None
+    o = Owner(8)
+    del o                                               # collected without free(): released by __del__
+    assert log == [(7, None), (8, None)]
+    b = Owner(9, borrowed=True)
+    b.free(); b.__del__()
+    assert len(log) == 2 and b.handle is None
+    half = Owner.__new__(Owner)
+    with pytest.raises(RuntimeError):
+        half.__init__(1, fail=True)
+    half.free(); half.__del__()                         # no handle was ever set: nothing to release, nothing raised
+    assert len(log) == 2
+    Owner(0).free()                                     # a null handle is not released either
+    assert len(log) == 2
+
+    class Raises(api._Handle):
+        def _release(self, h):
+            raise OSError('release failed')
+    r = Raises()
+    r.handle = 3
+    r.__del__()                                         # __del__ swallows it; free() itself does not
+    r.handle = 3
+    with pytest.raises(OSError):
+        r.free()
+    assert [cls for cls in (api.DeviceKey, api.DeviceR1cs, api.GateBlob, api.Gates, api.HostVk, api.PoseidonParams, api.MerkleTree, api._MultiHandle,
+                            api.Context, api.MultiContext) if not issubclass(cls, api._Handle) or '__del__' in vars(cls)] == []
+
+    g = api.Gates.__new__(api.Gates)
+    seen = []
+    g.lib = SimpleNamespace(fk_gates_free=lambda h: seen.append((h, g.handle)))
+    g.handle = 11
+    g.free(); g.free()
+    assert seen == [(11, None)]                         # the handle had left the object when the library was called
+
+    blob = api.GateBlob.__new__(api.GateBlob)
+    blob.lib = SimpleNamespace(fk_blob_free=lambda h: seen.append((h, blob.data)))
+    blob.handle, blob.data = 12, 'view'
+    blob.free()
+    assert seen[-1] == (12, None)                       # .data went first
+
+    freed = []
+    multi = SimpleNamespace(handle=21)
+    k1, k2 = (api._MultiHandle(multi, h, lambda m, h_: freed.append((m, h_))) for h in (31, 32))
+    k1.free(); k1.free()
+    multi.handle = None                                 # the MultiContext was closed
+    k2.free()
+    assert freed == [(21, 31), (None, 32)]
+
+    dk = api.DeviceKey(SimpleNamespace(handle=1, lib=SimpleNamespace(fk_key_free=lambda c, h: freed.append(('key', c, h)))), 41, borrowed=True)
+    dk.free()
+    assert freed[-1] == (None, 32) and 'free' not in vars(dk)          # a borrowed shard: no release, and no instance attribute named free
+    hv = api.HostVk.__new__(api.HostVk)
+    hv.lib, hv.handle = SimpleNamespace(fk_key_free=lambda c, h: freed.append(('key', c, h))), 51
+    del hv
+    assert freed[-1] == ('key', None, 51)               # fk_key_free(NULL, key)

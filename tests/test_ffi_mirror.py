@@ -2,7 +2,9 @@
 hand-written mirrors of include/fawkes_hip.h.  This test parses all three and fails on any difference in a function's name, arity,
 pointer / integer kind, pointee type or constness, and in the field order / widths of `fk_key_desc`; it compiles a C99 stub that prints
 sizeof / offsetof of the header's structs and compares them with the `#[repr(C)]` layout computed here from the Rust declaration and with
-the ctypes structures of fawkes-crypto_amd/api.py.  Reference interface: prover.rs:63-68 (what the shim's `prove` wraps), SURVEY 8(b)."""
+the ctypes structures of fawkes-crypto_amd/api.py.  The Python mirror's prototype table (fawkes-crypto_amd/_abi.py) is held to the header
+in the same way, to api.py's calls, and to what a loaded library carries.  Reference interface: prover.rs:63-68 (what the shim's `prove`
+wraps), SURVEY 8(b)."""
 import ctypes as C
 import os
 import re
@@ -252,3 +254,138 @@ def test_struct_layouts_c_vs_rust_vs_ctypes():
         assert C.sizeof(cls) == want.pop('size'), sname
         got = {f[0]: getattr(cls, f[0]).offset for f in cls._fields_}
         assert got == want, (sname, got, want)
+
+
+# ---------------------------------------------------------------- the ctypes prototype table (fawkes-crypto_amd/_abi.py)
+PY_STRUCTS = {'KeyDesc': 'fk_key_desc', 'Timings': 'fk_timings', 'R1csStruct': 'fk_r1cs', 'MsmPlanInfo': 'fk_msm_plan_info', 'MsmDynInfo': 'fk_msm_dyn_info'}
+
+
+def _abi():
+    sys.path.insert(0, ROOT)
+    from fawkes_crypto_amd import _abi
+    return _abi
+
+
+def _py_kind(t):
+    """ctypes type -> ('void',) | ('str',) | ('ptr', struct or None) | ('f64',) | ('int', signed, bytes).  c_size_t and c_uint64 are one
+    class on this ABI (as `usize` and `u64` are one width), so integers are compared by width and signedness."""
+    if t is None:
+        return ('void',)
+    if t is C.c_char_p:
+        return ('str',)
+    if t is C.c_void_p:
+        return ('ptr', None)
+    if issubclass(t, C._Pointer):
+        return ('ptr', PY_STRUCTS.get(t._type_.__name__, t._type_.__name__))
+    if t is C.c_double:
+        return ('f64',)
+    return ('int', t(-1).value < 0, C.sizeof(t))
+
+
+def _c_kind(ty, is_return=False):
+    """the header's type in the same terms; the table types only the five struct pointers, and `const char *` only as a return type"""
+    if ty[0] == 'ptr':
+        if is_return and ty[2] == 'char':
+            return ('str',)
+        return ('ptr', ty[2] if ty[2] in PY_STRUCTS.values() else None)
+    if ty[1] in ('void', 'f64'):
+        return (ty[1],)
+    return ('int', ty[1] == 'i32', {'i32': 4, 'u32': 4, 'u64': 8, 'usize': 8}[ty[1]])
+
+
+def _py_mirror_problems(table):
+    c_funcs, _ = parse_header()
+    problems = ['%s is declared in the header and missing from the table' % n for n in c_funcs if n not in table]
+    for name, (restype, argtypes) in table.items():
+        if name not in c_funcs:
+            problems.append('%s is in the table and not declared in include/fawkes_hip.h' % name)
+            continue
+        c_ret, c_params = c_funcs[name]
+        if _py_kind(restype) != _c_kind(c_ret, True):
+            problems.append('%s returns %s, the header says %s' % (name, _py_kind(restype), c_ret))
+        if len(argtypes) != len(c_params):
+            problems.append('%s takes %d arguments, the header %d' % (name, len(argtypes), len(c_params)))
+            continue
+        for t, (cn, ct) in zip(argtypes, c_params):
+            if _py_kind(t) != _c_kind(ct):
+                problems.append('%s argument %s is %s, the header has %s' % (name, cn, _py_kind(t), ct))
+    return problems
+
+
+def test_python_prototype_table_mirrors_the_header():
+    abi = _abi()
+    c_funcs, _ = parse_header()
+    assert len(abi.PROTOTYPES) == len(c_funcs) == 146 and set(abi.PROTOTYPES) == set(c_funcs)
+    problems = _py_mirror_problems(abi.PROTOTYPES)
+    assert not problems, '\n'.join(problems)
+    from fawkes_crypto_amd import api
+    assert api.EXPORTED_SYMBOLS == list(abi.PROTOTYPES)
+
+
+def test_the_table_check_notices_a_wrong_prototype():
+    """negative control: a dropped argument, a 32-bit integer for uint64_t, a value for a pointer, an untyped struct pointer, a missing
+    and an extra function are each reported, and nothing else is"""
+    abi = _abi()
+    good = dict(abi.PROTOTYPES)
+    ret, args = good['fk_key_synthetic']           # (ctx, u64 m, u32, u32, u64, u64, u64 seed, u32, u32, f64, f64, out)
+    assert args[1] is C.c_uint64 and args[-1] is C.c_void_p
+    for name, bad, said in (('fk_key_synthetic', (ret, args[:-1]), 'fk_key_synthetic takes 11 arguments, the header 12'),
+                            ('fk_key_synthetic', (ret, (args[0], C.c_uint32) + args[2:]), 'fk_key_synthetic argument m is'),
+                            ('fk_key_synthetic', (ret, args[:-1] + (C.c_uint64,)), 'fk_key_synthetic argument out is'),
+                            ('fk_key_synthetic', (None, args), 'fk_key_synthetic returns'),
+                            ('fk_msm_plan', (ret, good['fk_msm_plan'][1][:3] + (C.c_void_p,)), 'fk_msm_plan argument out is'),
+                            ('fk_poseidon_free', None, 'fk_poseidon_free is declared in the header and missing'),
+                            ('fk_poseidon_release', good['fk_poseidon_free'], 'fk_poseidon_release is in the table and not declared')):
+        table = dict(good)
+        if bad is None:
+            del table[name]
+        else:
+            table[name] = bad
+        problems = _py_mirror_problems(table)
+        assert len(problems) == 1 and problems[0].startswith(said), (said, problems)
+
+
+def test_every_prototype_is_called_by_api_py_or_listed_as_unwrapped():
+    """a new ABI function cannot be declared and forgotten, nor wrapped and left undeclared: the names api.py calls on the library and the
+    short list of entry points it leaves to `load_library()` users are, together and without overlap, the table"""
+    abi = _abi()
+    src = open(os.path.join(ROOT, 'fawkes-crypto_amd', 'api.py')).read()
+    called = set(re.findall(r'\.(fk_\w+)\b', src))
+    assert called - set(abi.PROTOTYPES) == set(), 'api.py calls what the table does not declare'
+    assert called & set(abi.NOT_WRAPPED) == set(), 'listed as unwrapped, yet called by api.py'
+    assert set(abi.PROTOTYPES) - called == set(abi.NOT_WRAPPED), sorted(set(abi.PROTOTYPES) - called - set(abi.NOT_WRAPPED))
+    assert len(abi.NOT_WRAPPED) <= 4
+
+
+def test_prototypes_are_applied_to_the_loaded_library():
+    """after load_library() every entry carries its argtypes, so a wrong call is refused before the library is entered (host-only entry
+    points: no GPU is involved)"""
+    import numpy as np
+    abi = _abi()
+    from fawkes_crypto_amd import api
+    lib = api.load_library()
+    for name, (restype, argtypes) in abi.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and tuple(fn.argtypes) == tuple(argtypes) and fn.restype is restype, name
+
+    class Lacking:                       # a library built from an older header: the failure names the symbol
+        def __getattr__(self, name):
+            if name == 'fk_msm_plan':
+                raise AttributeError(name)
+            return type('fn', (), {})()
+    with pytest.raises(AttributeError, match='does not export fk_msm_plan'):
+        abi.apply(Lacking())
+    info = api.MsmPlanInfo()
+    with pytest.raises(C.ArgumentError):
+        lib.fk_msm_plan(1.5, 0, 0, C.byref(info))                     # a float for a size_t
+    with pytest.raises(TypeError):
+        lib.fk_msm_plan(1 << 16, 0, 0)                                 # one argument too few
+    with pytest.raises(C.ArgumentError):
+        lib.fk_msm_plan(1 << 16, 0, 0, C.byref(api.MsmDynInfo()))      # another struct behind the typed pointer
+    lo, hi = C.c_uint64(), C.c_uint64()
+    with pytest.raises(C.ArgumentError):
+        lib.fk_shard_range(10, 0, 2, np.zeros(1, np.uint64), C.byref(hi))      # an ndarray is not a pointer: _vp(arr) is
+    assert info.n == 0
+    assert lib.fk_msm_plan(np.int64(1 << 16), np.uint32(0), False, C.byref(info)) == 0 and info.n == 1 << 16      # numpy integers and bools are
+    assert lib.fk_shard_range(np.uint64(10), 1, 2, C.byref(lo), C.byref(hi)) is None and (lo.value, hi.value) == api.shard_range(10, 1, 2)
+    assert api.msm_plan(1 << 16)['n'] == 1 << 16
