@@ -224,7 +224,7 @@ struct RoctxRange {
 
 // Tuning knobs.  A release build compiles the measured default in; `make EXP=1` (-DFK_EXPERIMENTS, libfawkes_hip_exp.so, loaded
 // with FK_LIB_VARIANT=exp) reads them from the environment for same-box A/B runs.  The run-time switches of a release build
-// are few and documented in DESIGN.md: FK_DEBUG, FK_MSM_PRECOMP, FK_MSM_PRE_MIN_LOG2, FK_PROVE_SORTS_FIRST, FK_SPMV_BIN_MIN,
+// are few and documented in DESIGN.md: FK_DEBUG, FK_MSM_PRECOMP, FK_MSM_PRE_MIN_LOG2, FK_PROVE_SORTS_FIRST, FK_SPMV_BIN_MIN, FK_SPMV_DEDUP,
 // FK_OVERLAP_WITNESS, FK_MULTI_HOST_EVENTS.
 static inline int tune(const char *name, int dflt) {
 #ifdef FK_EXPERIMENTS

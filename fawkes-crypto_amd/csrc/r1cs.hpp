@@ -57,6 +57,18 @@ struct fk_r1cs_dev {
     uint32_t win_k = 0;
     uint64_t win_row[WIN_MAX + 1] = {0}, win_need[WIN_MAX] = {0};
     uint32_t win_cnt[WIN_MAX + 1][fk::SPMV_SEGS] = {{0}};
+    // Repeated linear combinations (explicit systems, found once at load: spmv.hip, alias plan).  Row (dm, drow) of a binned matrix whose
+    // columns and coefficient indices are byte-identical to those of an earlier, non-alias row (sm, srow) at most alias_lookback gates
+    // back is an ALIAS: the unsliced evaluation leaves it out of the class lists (the dedup set: rowlist_dd / bins_dd / win_cnt_dd, the
+    // same class and block order as rowlist / bins / win_cnt) and spmv_alias_kernel copies out[sm][srow] to out[dm][drow] behind it.
+    // d_alias: drow | (drow - srow) << 32 | dm << 48 | sm << 50, sorted by (drow, dm); win_alias[j]: aliases whose drow < win_row[j].
+    // The sliced and the tiled evaluations and h_rowlist keep the full lists.
+    uint64_t *d_alias = nullptr, n_alias = 0, alias_terms = 0;
+    uint32_t alias_min = 0, alias_lookback = 0;
+    uint32_t *rowlist_dd[3] = {nullptr, nullptr, nullptr};       // only for the matrices that have aliases; bins_dd points at rowlist for the others
+    fk::BinArgs bins_dd;
+    uint32_t win_cnt_dd[WIN_MAX + 1][fk::SPMV_SEGS] = {{0}};
+    uint64_t win_alias[WIN_MAX + 1] = {0};
     // host copies of the class lists and the per-log_w residue-grouped variants, built on first use (fk_r1cs_eval_slice_dev)
     std::vector<uint32_t> h_rowlist[3];
     mutable fk::SliceLists slices[4];

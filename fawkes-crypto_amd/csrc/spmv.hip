@@ -24,6 +24,7 @@
 #include <string>
 
 #include "r1cs.hpp"
+#include "../../include/fawkes_hip_inspect.h"
 
 namespace fk {
 
@@ -209,6 +210,25 @@ __global__ __launch_bounds__(256) void col_window_max_kernel(const uint32_t *col
     if (any) atomicMax(&out[w], mx);
 }
 
+// Repeated linear combinations (r1cs.hpp: the alias plan): one lane per alias copies the value spmv_binned_kernel (or spmv_kernel, for a
+// source in a matrix that is not binned) wrote for the source row a moment ago on the same stream -- 8 + 32 + 32 bytes instead of a z
+// gather, a table load and a multiply-accumulate per term.  A source is never an alias itself, so the lanes do not depend on each other.
+__global__ __launch_bounds__(256) void spmv_alias_kernel(Fr *out0, Fr *out1, Fr *out2, const uint64_t *alias, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t e = alias[i];
+    const uint32_t drow = (uint32_t)e, srow = drow - ((uint32_t)(e >> 32) & 0xffffu), dm = (uint32_t)(e >> 48) & 3u, sm = (uint32_t)(e >> 50) & 3u;
+    const Fr *src = sm == 0 ? out0 : (sm == 1 ? out1 : out2);
+    Fr *dst = dm == 0 ? out0 : (dm == 1 ? out1 : out2);
+    dst[drow] = src[srow];
+}
+
+// FK_SPMV_DEDUP=0 (a run-time switch, read once): no alias plan at load, the full class lists and no alias kernel in the evaluation
+static bool spmv_dedup_on() {
+    static const bool on = !(getenv("FK_SPMV_DEDUP") && atoi(getenv("FK_SPMV_DEDUP")) == 0);
+    return on;
+}
+
 }  // namespace fk
 
 using namespace fk;
@@ -222,6 +242,8 @@ void fk_r1cs_free(fk_ctx *ctx, fk_r1cs_dev *r) {
     for (void *p : {(void *)r->table, (void *)r->d_a_aux, (void *)r->d_b_in, (void *)r->d_b_aux, (void *)r->d_idx_a, (void *)r->d_idx_b}) if (p) (void)hipFree(p);
     for (auto &sl : r->slices) for (uint32_t *p : sl.d_list) if (p) (void)hipFree(p);
     if (r->d_wavelist) (void)hipFree(r->d_wavelist);
+    for (uint32_t *p : r->rowlist_dd) if (p) (void)hipFree(p);
+    if (r->d_alias) (void)hipFree(r->d_alias);
     delete r;
 }
 
@@ -353,10 +375,13 @@ static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1
         }
         if (threw) { ctx->err = "r1cs: out of host memory while ordering the rows"; return fail(FK_ERR_OOM); }
     } else for (int k = 0; k < 3; k++) build_lists(k);
+    const bool want_alias = copies == 1 && spmv_dedup_on();     // the alias plan below reads the coefficient indices of all three matrices
+    std::vector<uint32_t> cidx_keep[3];
     for (int k = 0; k < 3 && rc == FK_OK; k++) {
         const uint64_t nnz = ptrs[k][cs->num_gates];
         r->nnz[k] = nnz * copies;
-        std::vector<uint32_t> cidx(trusted ? 1 : nnz ? nnz : 1);
+        std::vector<uint32_t> &cidx = cidx_keep[k];
+        cidx.resize(trusted ? 1 : nnz ? nnz : 1);
         Fr last = one; uint32_t last_idx = 0;        // one-entry cache in front of the hash map
         for (uint64_t i = 0; i < nnz && !trusted; i++) {
             uint32_t ci = 0;
@@ -389,6 +414,7 @@ static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1
         if (nnz && hipMemcpy(r->col[k], cols[k], nnz * 4, hipMemcpyHostToDevice) != hipSuccess) rc = FK_ERR_HIP;
         if (nnz && hipMemcpy(r->cidx[k], trusted ? pre_cidx[k] : cidx.data(), nnz * 4, hipMemcpyHostToDevice) != hipSuccess) rc = FK_ERR_HIP;
         t_copy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count();
+        if (pre_cidx || !want_alias) std::vector<uint32_t>().swap(cidx);
         // length classes (spmv_binned_kernel) when the matrix has long rows: planned above (build_lists)
         ListPlan &lp = plans[k];
         if (lp.binned && rc == FK_OK) {
@@ -447,6 +473,135 @@ static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1
             for (uint32_t j = 0; j < K; j++) { run = std::max<uint64_t>(run, (uint64_t)mx[j] + 1); r->win_need[j] = j + 1 == K ? nv : run; }
             r->win_k = K;
         }
+    }
+    // Alias plan: circuits repeat linear combinations (the Poseidon S-box multiplies a lazily expanded combination by itself: the B row of a
+    // gate equals its A row, or the A row two gates back) -- 29.6 % of the benchmark transaction's terms sit in such rows.  Which rows repeat is
+    // a property of the system, not of the witness, and out[dst] = out[src] holds for any z: found once here, see r1cs.hpp.  Gates in row
+    // order, matrices A, B, C inside a gate; a row of >= dd_min terms is an alias of the EARLIEST row, at most dd_back gates back, that has the
+    // same columns and coefficient indices (memcmp; the hash only finds candidates) and is not an alias itself.  Rows of a matrix that is not
+    // binned are sources only.  The bounded look-back makes it one streaming pass with O(dd_back) state, and src row <= dst row.
+    static const uint32_t dd_min = (uint32_t)std::max(1, tune("FK_SPMV_DEDUP_MIN", 4)), dd_back = (uint32_t)std::min(4096, std::max(0, tune("FK_SPMV_DEDUP_LOOKBACK", 8)));
+    r->alias_min = dd_min; r->alias_lookback = dd_back;
+    if (want_alias && r->bins.mask && cs->num_gates && cs->num_gates < 0xffffffffull) {
+        const uint64_t ng = cs->num_gates, NONE = ~0ull;
+        const uint32_t *h_cidx[3];
+        for (int k = 0; k < 3; k++) h_cidx[k] = pre_cidx ? pre_cidx[k] : cidx_keep[k].data();
+        // pass 1 (threads over blocks of gates, each reading dd_back gates into the block before it): the NEAREST earlier identical row of
+        // every row that has one -- independent of which rows end up as aliases.  key = gate * 3 + matrix.
+        struct Cand { uint64_t key, prev; };
+        auto scan = [&](uint64_t g0, uint64_t g1, std::vector<Cand> &found) {
+            const uint64_t R = (uint64_t)dd_back + 1;
+            std::vector<uint64_t> hs(R * 3), ln(R * 3, 0);              // ring over the last R gates; ln = 0: shorter than dd_min
+            for (uint64_t g = g0 > dd_back ? g0 - dd_back : 0; g < g1; g++) {
+                const size_t slot = (size_t)(g % R) * 3;
+                for (int k = 0; k < 3; k++) {
+                    const uint64_t lo = ptrs[k][g], len = ptrs[k][g + 1] - lo;
+                    ln[slot + k] = 0;
+                    if (len < dd_min) continue;
+                    uint64_t h = len;
+                    for (uint64_t i = 0; i < len; i++) h = (h ^ (cols[k][lo + i] | (uint64_t)h_cidx[k][lo + i] << 32)) * 0x9e3779b97f4a7c15ull + (h >> 31);
+                    hs[slot + k] = h; ln[slot + k] = len;
+                    if (g < g0) continue;
+                    auto same = [&](uint64_t g2, int k2) {
+                        const size_t s2 = (size_t)(g2 % R) * 3 + k2;
+                        if (ln[s2] != len || hs[s2] != h) return false;
+                        const uint64_t lo2 = ptrs[k2][g2];
+                        return memcmp(cols[k2] + lo2, cols[k] + lo, len * 4) == 0 && memcmp(h_cidx[k2] + lo2, h_cidx[k] + lo, len * 4) == 0;
+                    };
+                    uint64_t prev = NONE;
+                    for (int k2 = k - 1; k2 >= 0 && prev == NONE; k2--) if (same(g, k2)) prev = g * 3 + k2;
+                    for (uint64_t d = 1; d <= dd_back && d <= g && prev == NONE; d++)
+                        for (int k2 = 2; k2 >= 0 && prev == NONE; k2--) if (same(g - d, k2)) prev = (g - d) * 3 + k2;
+                    if (prev != NONE) found.push_back({g * 3 + k, prev});
+                }
+            }
+        };
+        const uint32_t n_thr = ng >= ((uint64_t)1 << 20) ? std::min(16u, std::max(1u, host_threads())) : 1u;
+        std::vector<std::vector<Cand>> found(n_thr);
+        std::vector<uint64_t> alias;                 // the device table's entries, in (dst row, dst matrix) order
+        std::vector<uint8_t> is_alias[3];
+        try {
+            std::atomic<bool> threw{false};
+            auto guarded = [&](uint32_t t) { try { scan(ng * t / n_thr, ng * (t + 1) / n_thr, found[t]); } catch (...) { threw = true; } };
+            {
+                std::vector<std::thread> pool;
+                for (uint32_t t = 1; t < n_thr; t++) { try { pool.emplace_back(guarded, t); } catch (...) { guarded(t); } }
+                guarded(0);
+                for (auto &th : pool) th.join();
+            }
+            if (threw) throw std::bad_alloc();
+            // pass 2 (serial, over the rows that have an identical predecessor only): walk the chain of identical rows back through the
+            // look-back and take the earliest one that is not an alias
+            struct Seen { uint64_t key, prev; bool alias; };
+            const uint64_t RS = 3 * ((uint64_t)dd_back + 1);
+            std::vector<Seen> ring(RS, Seen{NONE, NONE, false});
+            for (uint32_t t = 0; t < n_thr; t++) {
+                for (const Cand &c : found[t]) {
+                    const uint64_t g = c.key / 3; const uint32_t dm = (uint32_t)(c.key % 3);
+                    Seen &me = ring[c.key % RS];
+                    me = Seen{c.key, c.prev, false};
+                    if (!((r->bins.mask >> dm) & 1)) continue;
+                    uint64_t best = NONE;
+                    for (uint64_t cur = c.prev; cur != NONE && g - cur / 3 <= dd_back;) {
+                        const Seen &e = ring[cur % RS];
+                        const bool known = e.key == cur;         // not known: the row has no identical predecessor in ITS look-back, it is a source
+                        if (!known || !e.alias) best = cur;
+                        cur = known ? e.prev : NONE;
+                    }
+                    if (best == NONE) continue;
+                    me.alias = true;
+                    const uint64_t sg = best / 3, sm = best % 3;
+                    if (is_alias[dm].empty()) is_alias[dm].assign(ng, 0);
+                    is_alias[dm][g] = 1;
+                    alias.push_back(g | (g - sg) << 32 | (uint64_t)dm << 48 | sm << 50);
+                    r->alias_terms += ptrs[dm][g + 1] - ptrs[dm][g];
+                }
+                std::vector<Cand>().swap(found[t]);
+            }
+        } catch (...) { ctx->err = "r1cs: out of host memory while looking for repeated rows"; return fail(FK_ERR_OOM); }
+        if (!alias.empty()) {
+            // the dedup set: the class lists without the alias rows -- same class order, same block order, hence the same window prefixes
+            BinArgs &d = r->bins_dd;
+            d.mask = r->bins.mask;
+            std::vector<uint32_t> dd[3];
+            for (uint32_t s = 0; s < r->bins.nseg; s++) {
+                const uint32_t k = r->bins.mtx[s], nr = r->bins.n_rows[s];
+                const uint32_t *src = r->h_rowlist[k].data() + r->bins.list_off[s];
+                uint32_t off = r->bins.list_off[s], kept = nr;
+                const uint32_t *lo = src;
+                if (!is_alias[k].empty()) {
+                    off = (uint32_t)dd[k].size();
+                    for (uint32_t i = 0; i < nr; i++) if (!is_alias[k][src[i]]) dd[k].push_back(src[i]);
+                    kept = (uint32_t)dd[k].size() - off;
+                }
+                if (!kept) continue;
+                const uint32_t sd = d.nseg++;
+                const uint64_t per = 256u >> r->bins.lg[s];
+                d.lg[sd] = r->bins.lg[s]; d.mtx[sd] = k; d.n_rows[sd] = kept; d.list_off[sd] = off;
+                d.first_block[sd + 1] = d.first_block[sd] + (uint32_t)((kept + per - 1) / per);
+                if (!is_alias[k].empty()) lo = dd[k].data() + off;          // (dd[k] grows no more inside this iteration)
+                for (uint32_t j = 0; j <= r->win_k && r->win_k; j++) {
+                    const uint64_t bound = r->win_row[j];
+                    r->win_cnt_dd[j][sd] = (uint32_t)(std::partition_point(lo, lo + kept, [&](uint32_t row) { return row < bound; }) - lo);
+                }
+            }
+            for (uint32_t j = 0; j <= r->win_k && r->win_k; j++) {
+                const uint64_t bound = r->win_row[j];
+                r->win_alias[j] = (uint64_t)(std::partition_point(alias.begin(), alias.end(), [&](uint64_t e) { return (e & 0xffffffffull) < bound; }) - alias.begin());
+            }
+            for (int k = 0; k < 3; k++) {
+                d.rowlist[k] = r->rowlist[k];
+                if (is_alias[k].empty()) continue;
+                if (hipMalloc((void **)&r->rowlist_dd[k], dd[k].size() * 4 + 4) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
+                if (!dd[k].empty() && hipMemcpy(r->rowlist_dd[k], dd[k].data(), dd[k].size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
+                d.rowlist[k] = r->rowlist_dd[k];
+            }
+            if (hipMalloc((void **)&r->d_alias, alias.size() * 8) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
+            if (hipMemcpy(r->d_alias, alias.data(), alias.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
+            r->n_alias = alias.size();
+        }
+        if (getenv("FK_GATES_TRACE")) fprintf(stderr, "[fk] r1cs load: %.2f s so far, alias plan done (%llu aliases for %llu terms)\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_load0).count(),
+                                              (unsigned long long)r->n_alias, (unsigned long long)r->alias_terms);
     }
     if (copies > 1 && wave_copies && copies >= wave_copies && r->bins.mask && cs->num_gates < ((uint64_t)1 << 30)) {
         std::vector<uint32_t> wl;
@@ -539,6 +694,28 @@ int fk_r1cs_info(const fk_r1cs_dev *r, uint64_t out[8]) {
     return FK_OK;
 }
 
+// inspection for the tests: the alias plan of a resident system (r1cs.hpp)
+int fk_r1cs_alias_info(const fk_r1cs_dev *r, uint64_t out[4]) {
+    if (!r || !out) return FK_ERR_BAD_ARG;
+    out[0] = r->n_alias; out[1] = r->n_alias ? r->alias_terms : 0; out[2] = r->alias_min; out[3] = r->alias_lookback;
+    return FK_OK;
+}
+
+int fk_r1cs_aliases(const fk_r1cs_dev *r, uint64_t cap, uint32_t *dst_mtx, uint32_t *dst_row, uint32_t *src_mtx, uint32_t *src_row) {
+    if (!r || !dst_mtx || !dst_row || !src_mtx || !src_row || cap < r->n_alias) return FK_ERR_BAD_ARG;
+    if (!r->n_alias) return FK_OK;
+    try {
+        std::vector<uint64_t> h(r->n_alias);
+        if (hipMemcpy(h.data(), r->d_alias, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return FK_ERR_HIP;
+        for (uint64_t i = 0; i < h.size(); i++) {
+            const uint64_t e = h[i];
+            dst_row[i] = (uint32_t)e; src_row[i] = (uint32_t)e - ((uint32_t)(e >> 32) & 0xffffu);
+            dst_mtx[i] = (uint32_t)(e >> 48) & 3u; src_mtx[i] = (uint32_t)(e >> 50) & 3u;
+        }
+    } catch (...) { return FK_ERR_OOM; }
+    return FK_OK;
+}
+
 int fk_r1cs_windows(const fk_r1cs_dev *r, uint32_t *n_windows, uint64_t rows[17], uint64_t need[16]) {
     if (!r || !n_windows) return FK_ERR_BAD_ARG;
     *n_windows = r->win_k;
@@ -614,8 +791,10 @@ int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a
         else { if (sliced) FK_SPMV_LAUNCH(false, true); else FK_SPMV_LAUNCH(false, false); }
 #undef FK_SPMV_LAUNCH
     }
+    // explicit system, unsliced: the class lists without the alias rows, then the aliases copied from their sources (r1cs.hpp)
+    const bool dedup = r->n_alias && !tiled && !sliced && spmv_dedup_on();
     if (binned) {
-        BinArgs b = r->bins;
+        BinArgs b = dedup ? r->bins_dd : r->bins;
         SliceArgs sa;
         if (sliced) {
             // this rank's plan: copy c needs the rows = rank - c * base_gates (mod W); the residues repeat every P copies
@@ -660,7 +839,7 @@ int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a
         if (window >= 0) {
             b.first_block[0] = 0;
             for (uint32_t s = 0; s < b.nseg; s++) {
-                const uint32_t c0 = r->win_cnt[window][s], c1 = r->win_cnt[window + 1][s];
+                const uint32_t c0 = (dedup ? r->win_cnt_dd : r->win_cnt)[window][s], c1 = (dedup ? r->win_cnt_dd : r->win_cnt)[window + 1][s];
                 b.list_off[s] += c0; b.n_rows[s] = c1 - c0;
                 const uint64_t per = 256u >> b.lg[s];
                 b.first_block[s + 1] = b.first_block[s] + (uint32_t)((b.n_rows[s] + per - 1) / per);
@@ -673,6 +852,10 @@ int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a
             if (tiled) { if (sliced) FK_SPMVB_LAUNCH(true, true); else FK_SPMVB_LAUNCH(true, false); }
             else { if (sliced) FK_SPMVB_LAUNCH(false, true); else FK_SPMVB_LAUNCH(false, false); }
 #undef FK_SPMVB_LAUNCH
+        }
+        if (dedup) {
+            const uint64_t a0 = window >= 0 ? r->win_alias[window] : 0, a1 = window >= 0 ? r->win_alias[window + 1] : r->n_alias;      // dst in this window: src in it or an earlier one
+            if (a1 > a0) hipLaunchKernelGGL(spmv_alias_kernel, dim3((unsigned)((a1 - a0 + 255) / 256)), dim3(256), 0, ctx->stream, a.out[0], a.out[1], a.out[2], r->d_alias + a0, a1 - a0);
         }
     }
     FK_HIP(ctx, hipGetLastError());
