@@ -19,3 +19,4 @@ from .api import (  # noqa: F401
 from . import parallel  # noqa: F401
 from . import params_io  # noqa: F401
 from . import witness  # noqa: F401
+from . import verify_agg  # noqa: F401

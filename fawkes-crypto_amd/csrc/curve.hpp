@@ -132,6 +132,20 @@ struct alignas(16) Xyzz {
         }
         return acc;
     }
+
+    // k * p for an affine p and a k of at most 128 bits, k = hi 2^64 + lo: `nbits` double-and-add steps from bit nbits - 1 down, mixed
+    // additions.  The scalar is walked by shifting it left -- no run-time index into a register array, so nothing goes to scratch.
+    static FK_HD Xyzz mul_affine_bits(const Affine<F> &p, uint64_t lo, uint64_t hi, int nbits) {
+        Xyzz acc = inf();
+        if (p.is_inf()) return acc;
+        for (int s = 128 - nbits; s > 0; s--) { hi = hi << 1 | lo >> 63; lo <<= 1; }
+        for (int i = 0; i < nbits; i++) {
+            acc = dbl(acc);
+            if (hi >> 63) acc.add_mixed_nz(p);
+            hi = hi << 1 | lo >> 63; lo <<= 1;
+        }
+        return acc;
+    }
 };
 
 template <class F>

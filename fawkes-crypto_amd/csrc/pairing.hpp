@@ -39,6 +39,13 @@ struct Fq6T {
         const F2 t02 = F2::sub(F2::sub(F2::mul(F2::add(a.c0, a.c2), F2::add(b.c0, b.c2)), a0b0), a2b2);   // a0b2 + a2b0
         return Fq6T{F2::add(a0b0, mul_xi(t12)), F2::add(t01, mul_xi(a2b2)), F2::add(t02, a1b1)};
     }
+    // a (b0 + b1 v): the sparse operand of a line (Fq12T::mul_by_line), 5 Fq2 products instead of 9
+    static FK_HD Fq6T mul_by_01(const Fq6T &a, const F2 &b0, const F2 &b1) {
+        const F2 t0 = F2::mul(a.c0, b0), t1 = F2::mul(a.c1, b1);
+        const F2 t01 = F2::sub(F2::sub(F2::mul(F2::add(a.c0, a.c1), F2::add(b0, b1)), t0), t1);          // a0b1 + a1b0
+        return Fq6T{F2::add(t0, mul_xi(F2::mul(a.c2, b1))), t01, F2::add(t1, F2::mul(a.c2, b0))};
+    }
+    static FK_HD Fq6T mul_by_fq2(const Fq6T &a, const F2 &b) { return Fq6T{F2::mul(a.c0, b), F2::mul(a.c1, b), F2::mul(a.c2, b)}; }
     static FK_HD Fq6T mul_v(const Fq6T &a) { return Fq6T{mul_xi(a.c2), a.c0, a.c1}; }
     static FK_HD Fq6T inv(const Fq6T &a) {
         const F2 t0 = F2::sub(F2::sqr(a.c0), mul_xi(F2::mul(a.c1, a.c2)));
@@ -63,6 +70,19 @@ struct Fq12T {
         return Fq12T{F6::add(aa, F6::mul_v(bb)), cross};
     }
     static FK_HD Fq12T sqr(const Fq12T &a) { return mul(a, a); }
+    // a^2 as a "complex" square over Fq6: c0 = (a0 + a1)(a0 + v a1) - a0a1 - v a0a1, c1 = 2 a0a1 -- two Fq6 products (12 Fq2) for mul's three (18)
+    static FK_HD Fq12T sqr_complex(const Fq12T &a) {
+        const F6 ab = F6::mul(a.c0, a.c1);
+        const F6 t = F6::mul(F6::add(a.c0, a.c1), F6::add(a.c0, F6::mul_v(a.c1)));
+        return Fq12T{F6::sub(F6::sub(t, ab), F6::mul_v(ab)), F6::add(ab, ab)};
+    }
+    // a * (l0 + l1 w + l3 w^3): a line of miller_loop_proj has three nonzero Fq2 coefficients out of six, as an Fq12 it is
+    // (l0, 0, 0) + (l1, l3, 0) w.  Karatsuba over w with the sparse Fq6 products: 3 + 5 + 5 = 13 Fq2 products for mul's 18.
+    static FK_HD Fq12T mul_by_line(const Fq12T &a, const F2 &l0, const F2 &l1, const F2 &l3) {
+        const F6 aa = F6::mul_by_fq2(a.c0, l0), bb = F6::mul_by_01(a.c1, l1, l3);
+        const F6 cross = F6::sub(F6::sub(F6::mul_by_01(F6::add(a.c0, a.c1), F2::add(l0, l1), l3), aa), bb);
+        return Fq12T{F6::add(aa, F6::mul_v(bb)), cross};
+    }
     static FK_HD Fq12T conj(const Fq12T &a) { return Fq12T{a.c0, F6::neg(a.c1)}; }     // a^(p^6)
     static FK_HD Fq12T inv(const Fq12T &a) {
         const F6 d = F6::inv(F6::sub(F6::mul(a.c0, a.c0), F6::mul_v(F6::mul(a.c1, a.c1))));
@@ -113,6 +133,69 @@ static FK_HD Fq12T<Fq> miller_loop(const Affine<Fq> &P, const Affine<Fq2T<Fq>> &
             yr = F2::sub(F2::mul(lam2, F2::sub(xr, x4)), yr);
             xr = x4;
         }
+    }
+    return f;
+}
+
+// The same ate loop (T = 6 x^2, the same bits) with the running point R = (X : Y : Z) in homogeneous projective coordinates on the
+// twist (x = X / Z, y = Y / Z) and NO inversion in a step.  P in G1 (affine), Q on the twist (affine, of prime order r).
+//
+// The tower is Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - xi), xi = 9 + u, and the D-type twist E': y^2 = x^3 + b', b' = 3 / xi,
+// is untwisted by psi(x, y) = (x w^2, y w^3).  The line through psi(R) with twist slope lambda, at P = (xP, yP), is (miller_loop)
+//     l = yP - lambda xP w + (lambda xR - yR) w^3.
+// Doubling: lambda = 3 xR^2 / (2 yR) = 3 X^2 / (2 Y Z), and lambda xR - yR = (3 X^3 - 2 Y^2 Z) / (2 Y Z^2) = (Y^2 - 3 b' Z^2) / (2 Y Z)
+// by the curve equation Y^2 Z = X^3 + b' Z^3.  Scaled by 2 Y Z:
+//     l' = 2 Y Z yP - 3 X^2 xP w + (Y^2 - 3 b' Z^2) w^3.
+// With B = Y^2, C = Z^2, E = 3 b' C, F = 3 E, H = 2 Y Z, the double is (from x3 = x (y^2 - 9 b') / (4 y^2) and
+// y3 = (y^4 + 18 b' y^2 - 27 b'^2) / (8 y^3), cleared of denominators over the common Z3)
+//     X3 = 2 X Y (B - F),   Y3 = (B + F)^2 - 12 E^2,   Z3 = 4 B H.
+// Addition of Q = (x2, y2): theta = Y - y2 Z, mu = X - x2 Z, slope theta / mu; the line through Q scaled by mu:
+//     l' = mu yP - theta xP w + (theta x2 - mu y2) w^3,
+// and with c = theta^2, d = mu^2, e = mu d, g = X d, h = e + Z c - 2 g:  X3 = mu h,  Y3 = theta (g - h) - e Y,  Z3 = Z e.
+// mu != 0 because R = +-Q never happens for a Q of prime order r > T.
+//
+// Every line is thus the affine line times a nonzero element of Fq2 (2 Y Z, or mu).  Fq2 is a proper subfield of Fq12 and
+// (p^12 - 1) / r is a multiple of p^6 - 1, hence of p^2 - 1 = |Fq2*|: the final exponentiation sends each factor to one, so
+// miller_loop_proj and miller_loop agree AFTER final_exponentiation (not before).  P stays affine: an (X, Y, Z) form of P would scale
+// two more coefficients by Z in each of the ~190 lines, 380 Fq products -- what the one Fermat inversion of w A costs -- and hold a
+// third coordinate live through a loop that is already short of registers; the inversion sits in agg_prepare_kernel instead.
+// Fq2 products: doubling step 10 for the point and E, 4 Fq for the line; addition step 11 for the point, 2 + 4 Fq for the line;
+// f^2 12 (sqr_complex), f * line 13 (mul_by_line).
+// The bits are walked by shifting the 128-bit image of T left: the words live in scalar registers, the branch is wave-uniform.
+template <class Fq>
+static FK_HD Fq12T<Fq> miller_loop_proj(const Affine<Fq> &P, const Affine<Fq2T<Fq>> &Q) {
+    using F2 = Fq2T<Fq>; using F12 = Fq12T<Fq>;
+    F12 f = F12::one();
+    if (P.is_inf() || Q.is_inf()) return f;
+    const uint32_t T[4] = FK_ATE_LOOP_T, b0[8] = FK_G2_B0, b1[8] = FK_G2_B1;
+    F2 bt;
+    for (int i = 0; i < 8; i++) { bt.c0.v[i] = b0[i]; bt.c1.v[i] = b1[i]; }
+    const F2 b3 = F2::add(F2::dbl(bt), bt);                           // 3 b'
+    auto by_fq = [](const F2 &a, const Fq &k) { return F2{Fq::mul(a.c0, k), Fq::mul(a.c1, k)}; };
+    F2 X = Q.x, Y = Q.y, Z = F2::one();
+    uint64_t hi = (uint64_t)T[3] << 32 | T[2], lo = (uint64_t)T[1] << 32 | T[0];
+    int left = 128;
+    do { const bool top = hi >> 63; hi = hi << 1 | lo >> 63; lo <<= 1; left--; if (top) break; } while (left);     // past the leading one
+    for (; left > 0; left--) {
+        {   // doubling step
+            const F2 B = F2::sqr(Y), C = F2::sqr(Z), J = F2::sqr(X), A = F2::mul(X, Y), H = F2::dbl(F2::mul(Y, Z));
+            const F2 E = F2::mul(b3, C), F = F2::add(F2::dbl(E), E);
+            f = F12::mul_by_line(F12::sqr_complex(f), by_fq(H, P.y), F2::neg(by_fq(F2::add(F2::dbl(J), J), P.x)), F2::sub(B, E));
+            const F2 EE = F2::sqr(E), EE4 = F2::dbl(F2::dbl(EE));
+            X = F2::dbl(F2::mul(A, F2::sub(B, F)));
+            Y = F2::sub(F2::sqr(F2::add(B, F)), F2::add(F2::dbl(EE4), EE4));
+            Z = F2::dbl(F2::dbl(F2::mul(B, H)));
+        }
+        if (hi >> 63) {   // addition step with Q
+            const F2 theta = F2::sub(Y, F2::mul(Q.y, Z)), mu = F2::sub(X, F2::mul(Q.x, Z));
+            f = F12::mul_by_line(f, by_fq(mu, P.y), F2::neg(by_fq(theta, P.x)), F2::sub(F2::mul(theta, Q.x), F2::mul(mu, Q.y)));
+            const F2 c = F2::sqr(theta), d = F2::sqr(mu), e = F2::mul(mu, d), g = F2::mul(X, d);
+            const F2 h = F2::sub(F2::add(e, F2::mul(Z, c)), F2::dbl(g));
+            X = F2::mul(mu, h);
+            Y = F2::sub(F2::mul(theta, F2::sub(g, h)), F2::mul(e, Y));
+            Z = F2::mul(Z, e);
+        }
+        hi = hi << 1 | lo >> 63; lo <<= 1;
     }
     return f;
 }

@@ -7,33 +7,9 @@
 // Wire formats are the reference's: the verifying key as fawkes' Borsh `VK` (verifier.rs:46-54: alpha (G1), beta, gamma,
 // delta (G2), u32 LE count, ic (G1); every coordinate the canonical little-endian integer, group.rs:16-50), the proof as
 // the 256-byte Borsh `Proof` (prover.rs:39-45), the public inputs as `Num<Fr>` (Montgomery limbs), without the leading ONE.
-#include "common.hpp"
-#include "pairing.hpp"
-#include <string.h>
+#include "verify_decode.hpp"      // the Borsh decoders and vk_check, shared with verify_agg.hip
 
 namespace fk {
-
-template <class Fq>
-static FK_HD Fq canon_to_mont(const uint8_t *p, bool *ok) {
-    Fq v;
-    for (int i = 0; i < 8; i++) v.v[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    bool below = false;
-    for (int i = 7; i >= 0; i--) {
-        if (v.v[i] < FqParams::p(i)) { below = true; break; }
-        if (v.v[i] > FqParams::p(i)) break;
-    }
-    if (!below) *ok = false;                       // Num<Fq>::deserialize: from_uint fails for values >= q
-    return Fq::to_mont(v);
-}
-template <class Fq>
-static FK_HD Affine<Fq> g1_from_borsh(const uint8_t *p, bool *ok) { return Affine<Fq>{canon_to_mont<Fq>(p, ok), canon_to_mont<Fq>(p + 32, ok)}; }
-template <class Fq>
-static FK_HD Affine<Fq2T<Fq>> g2_from_borsh(const uint8_t *p, bool *ok) {
-    Affine<Fq2T<Fq>> a;
-    a.x.c0 = canon_to_mont<Fq>(p, ok); a.x.c1 = canon_to_mont<Fq>(p + 32, ok);
-    a.y.c0 = canon_to_mont<Fq>(p + 64, ok); a.y.c1 = canon_to_mont<Fq>(p + 96, ok);
-    return a;
-}
 
 // vk: Borsh bytes (alpha 64 | beta 128 | gamma 128 | delta 128 | u32 n_ic | n_ic x 64); inputs: n_ic - 1 Montgomery Fr
 // returns 1 accept, 0 reject, -1 malformed encoding
@@ -74,16 +50,6 @@ __global__ __launch_bounds__(64) void verify_batch_kernel(const uint8_t *vk, uin
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     out[i] = (int8_t)verify_one<FqC, FrC>(vk, n_ic, inputs + (size_t)i * (n_ic - 1), proofs + (size_t)i * FK_PROOF_BYTES);
-}
-
-static int vk_check(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, uint32_t n_inputs, uint32_t *n_ic) {
-    if (!vk || vk_len < 456) FK_SET_ERR(ctx, FK_ERR_FORMAT, "verify: verifying key truncated");
-    uint32_t n; memcpy(&n, vk + 448, 4);
-    if (vk_len != 452 + (size_t)n * 64) FK_SET_ERR(ctx, FK_ERR_FORMAT, "verify: verifying key holds %u ic points but is %zu bytes long", n, vk_len);
-    // bellman verify_proof: (public_inputs.len() + 1) != pvk.ic.len() -> SynthesisError::MalformedVerifyingKey
-    if (n != n_inputs + 1) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "verify: %u public inputs for a key with %u ic points", n_inputs, n);
-    *n_ic = n;
-    return FK_OK;
 }
 
 }  // namespace fk
