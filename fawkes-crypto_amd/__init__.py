@@ -20,3 +20,4 @@ from . import parallel  # noqa: F401
 from . import params_io  # noqa: F401
 from . import witness  # noqa: F401
 from . import verify_agg  # noqa: F401
+from . import check  # noqa: F401

@@ -131,6 +131,7 @@ struct fk_ctx {
     hipEvent_t ev_chunk[16] = {nullptr};      // fk_prove_r1cs, chunked hand-over: piece j of the witness has landed (spmv.hip)
     // NTT / prover scratch
     fk::DevBuf ntt_s1, ntt_s2, ntt_io, hbuf, sc_a, sc_b, scan_tmp, stage_a, stage_b, stage_c, stage_z, stage_d;
+    fk::DevBuf check;     // check.hip: the counters of an R1CS check, then the bitmap and the group flags the caller did not ask for
     // stats
     std::vector<fk::EventPair> ev_acc, ev_acc2, ev_ntt;   // G1 accumulate, G2 accumulate, NTT passes
     std::vector<hipEvent_t> ev_pool;

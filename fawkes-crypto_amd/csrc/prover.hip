@@ -121,7 +121,7 @@ void fk_free(fk_ctx *ctx) {
     msm_release(ctx);
     for (DevBuf *b : {&ctx->misc, &ctx->ntt_s1, &ctx->ntt_s2, &ctx->ntt_io,
                       &ctx->hbuf, &ctx->sc_a, &ctx->sc_b, &ctx->scan_tmp, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c,
-                      &ctx->stage_z, &ctx->stage_d})
+                      &ctx->stage_z, &ctx->stage_d, &ctx->check})
         b->release();
     for (auto &v : {&ctx->ev_acc, &ctx->ev_acc2, &ctx->ev_ntt}) for (auto &ep : *v) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -150,7 +150,7 @@ int fk_trim(fk_ctx *ctx) { return fk_guard(ctx, [&]() -> int {
     ntt_free_domains(ctx);
     msm_release(ctx);
     for (DevBuf *b : {&ctx->misc, &ctx->ntt_s1, &ctx->ntt_s2, &ctx->ntt_io, &ctx->hbuf, &ctx->sc_a, &ctx->sc_b, &ctx->scan_tmp, &ctx->stage_a, &ctx->stage_b,
-                      &ctx->stage_c, &ctx->stage_z, &ctx->stage_d})
+                      &ctx->stage_c, &ctx->stage_z, &ctx->stage_d, &ctx->check})
         b->release();
     for (auto &w : ctx->wslot) { w.buf.release(); w.deferred = false; if (w.ready) { (void)hipEventDestroy(w.ready); w.ready = nullptr; } if (w.part) { (void)hipEventDestroy(w.part); w.part = nullptr; } }      // "holds nothing" again
     ctx->lane_prev = 0; ctx->lane_next = 0;

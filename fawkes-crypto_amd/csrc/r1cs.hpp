@@ -74,3 +74,10 @@ struct fk_r1cs_dev {
     mutable fk::SliceLists slices[4];
     mutable std::mutex slice_mu;
 };
+
+namespace fk {
+// spmv.hip
+int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a, void *d_b, void *d_c, bool sliced, uint32_t rank, uint32_t log_w, uint64_t n_out, int window);
+int prove_r1cs_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
+                        uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval);
+}  // namespace fk

@@ -883,11 +883,14 @@ int fk_r1cs_eval_slice_dev(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, u
     return r1cs_eval_impl(ctx, r, d_z, d_a, d_b, d_c, true, rank, log_w, (uint64_t)1 << (log_m - log_w));
 }); }
 
-// witness in -> proof out: SpMV, quotient, MSMs, assembly.  z: device pointer (num_input + num_aux elements).
-int fk_prove_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
-                      uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
-    FK_RANGE("fk_prove_r1cs_dev");
-    if (!ctx) return FK_ERR_BAD_ARG;
+}  // extern "C"
+namespace fk {
+// The body of fk_prove_r1cs_dev, shared with fk_prove_r1cs_checked_dev (check.hip).  after_eval (may be null): called once the evaluation
+// of a, b, c into the stage buffers is queued on the main stream and before the quotient that consumes them is; what it queues there
+// reads the very a, b, c the proof is made from.  An entry that passes one does not join the submit / wait pipeline: any outstanding
+// early front is refused.  With a null after_eval nothing differs from the body as it stood: same calls, same order.
+int prove_r1cs_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
+                        uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval) {
     if (!key || !r || !d_z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
     if (r->num_input != key->num_input || r->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
     const uint64_t rows = r->num_gates + r->num_input;
@@ -895,6 +898,7 @@ int fk_prove_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, cons
                                                                      (unsigned long long)rows, (unsigned long long)key->m);
     FK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t mb = key->m * sizeof(Fr);
+    if (after_eval && ctx->early.done) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: an early front of a submitted proof is outstanding"); }
     if (ctx->early.done && ctx->early.key == key && ctx->early.r1cs == r && ctx->early.d_z == d_z) {
         // the front of this proof -- ev_z, the evaluation of a, b, c into the stage buffers, the witness multiplications' sorts --
         // was queued while the previous proof's tails ran (early_front below): go on with the quotient
@@ -916,12 +920,23 @@ int fk_prove_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, cons
         ctx->ev_z_recorded = true;
     }
     ctx->qidx = &r->qidx;      // the queries' index lists are known: no per-proof density compaction
-    const int rce = fk_r1cs_eval_dev(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p);
+    int rce = fk_r1cs_eval_dev(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p);
+    if (rce == FK_OK && after_eval) rce = (*after_eval)();
     if (rce != FK_OK) { ctx->qidx = nullptr; ctx->ev_z_recorded = false; return rce; }
     const int rc = fk_prove_dev(ctx, key, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, rows, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux, rr, ss, out_proof, tm);
     ctx->qidx = nullptr;
     ctx->ev_z_recorded = false;
     return rc;
+}
+}  // namespace fk
+extern "C" {
+
+// witness in -> proof out: SpMV, quotient, MSMs, assembly.  z: device pointer (num_input + num_aux elements).
+int fk_prove_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
+                      uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
+    FK_RANGE("fk_prove_r1cs_dev");
+    if (!ctx) return FK_ERR_BAD_ARG;
+    return prove_r1cs_dev_impl(ctx, key, r, d_z, rr, ss, out_proof, tm, nullptr);
 }); }
 
 // multi-GPU: all five multiplications of this key's slices for a resident constraint system (see fk_prove_msms_hz_dev)
