@@ -21,3 +21,4 @@ from . import params_io  # noqa: F401
 from . import witness  # noqa: F401
 from . import verify_agg  # noqa: F401
 from . import check  # noqa: F401
+from . import merkle  # noqa: F401

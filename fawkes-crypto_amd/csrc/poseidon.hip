@@ -45,12 +45,6 @@ __global__ __launch_bounds__(POS_THREADS) void poseidon_sponge_kernel(const Fr *
     out[i] = s[0];
 }
 
-static __device__ __forceinline__ Fr hash2(const Fr *__restrict__ tab, uint32_t f, uint32_t p, const Fr &a, const Fr &b) {
-    Fr s[3] = {a, b, Fr::zero()};
-    PoseidonPerm<3>::run(s, tab, f, p);
-    return s[0];
-}
-
 // one Merkle level: out[i] = H(in[2 i], in[2 i + 1]), n_out parents
 __global__ __launch_bounds__(POS_THREADS) void poseidon_level_kernel(const Fr *__restrict__ tab, uint32_t f, uint32_t p, const Fr *__restrict__ in, size_t n_out,
                                                                       Fr *__restrict__ out) {

@@ -82,6 +82,12 @@ struct PoseidonPerm {
     }
 };
 
+static __device__ __forceinline__ Fr hash2(const Fr *__restrict__ tab, uint32_t f, uint32_t p, const Fr &a, const Fr &b) {
+    Fr s[3] = {a, b, Fr::zero()};
+    PoseidonPerm<3>::run(s, tab, f, p);
+    return s[0];
+}
+
 // ------------------------------------------------------------------------------------------ host: Keccak-256, ChaCha20 (published specifications)
 static inline uint64_t rol64(uint64_t v, unsigned n) { n &= 63; return n ? (v << n) | (v >> (64 - n)) : v; }
 
