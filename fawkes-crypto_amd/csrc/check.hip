@@ -264,9 +264,7 @@ int fk_r1cs_check_dev(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, uint64
     FK_RANGE("fk_r1cs_check_dev");
     if (!ctx) return FK_ERR_BAD_ARG;
     FK_TRY(check_args(ctx, r, d_z, group_rows, d_group_bad, rep));
-    // the stage buffers hold the a, b, c of a submitted proof whose front ran early: they are not this call's to overwrite
-    if (ctx->early.done) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: an early front of a submitted proof is outstanding (call fk_prove_r1cs_wait first)");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "check"));      // the stage buffers may hold the a, b, c of a submitted proof whose front ran early
     CheckPlan p;
     FK_TRY(check_plan(ctx, r, group_rows, d_bad_bitmap, d_group_bad, &p));
     const size_t rb = ((size_t)r->num_gates + r->num_input) * sizeof(Fr);

@@ -8,8 +8,10 @@
 #include <string>
 #include <new>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 #include <functional>
+#include <initializer_list>
 #include "../../include/fawkes_hip.h"
 #include "curve.hpp"
 
@@ -31,6 +33,20 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *)p; }
 };
+
+// The context's grow-only scratch as ONE set: fk_free and fk_trim walk it, so a buffer added here is released by both.  DevBuf members
+// only (the walk below is over them); the MSM lanes keep their own (MsmLane, msm_release).
+struct CtxScratch {
+    DevBuf misc;      // small per-call tables and records (no proof keeps anything here between two calls)
+    // NTT / prover scratch.  stage_a .. stage_d, stage_z are the buffers a proof is staged in: between two calls of the submit / wait
+    // pipeline they hold the NEXT proof's a, b, c (early front, fk_ctx::early) -- every other entry borrows them through scratch_claim
+    DevBuf ntt_s1, ntt_s2, ntt_io, hbuf, sc_a, sc_b, scan_tmp, stage_a, stage_b, stage_c, stage_z, stage_d;
+    DevBuf check;     // check.hip: the counters of an R1CS check, then the bitmap and the group flags the caller did not ask for
+    DevBuf *begin() { return &misc; }
+    DevBuf *end() { return begin() + sizeof(CtxScratch) / sizeof(DevBuf); }
+    void release_scratch() { for (DevBuf *b = begin(); b != end(); ++b) b->release(); }
+};
+static_assert(std::is_standard_layout<CtxScratch>::value && sizeof(CtxScratch) % sizeof(DevBuf) == 0, "CtxScratch holds DevBuf members and nothing else");
 
 struct NttDomain;
 
@@ -81,7 +97,7 @@ struct KeyPre {
 
 }  // namespace fk
 
-struct fk_ctx {
+struct fk_ctx : fk::CtxScratch {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -94,7 +110,6 @@ struct fk_ctx {
     int co_tenants = 1;                   // contexts of one fk_multi that share this device (ranks on one GPU: tests, rehearsals): each needs its own scratch
     int lanes_in_use = fk::MSM_LANES;   // the provers use 2 for the largest domains (measured, prover.hip)
     fk::MsmTail tails[fk::MSM_TAILS];
-    fk::DevBuf misc;
     // witness multiplications (L, A, B1, B2) in flight: begun before / while the quotient runs on the main stream
     hipStream_t aux = nullptr;          // scalar compaction for the A / B queries
     hipEvent_t ev_aux = nullptr, ev_main = nullptr, ev_z = nullptr;
@@ -129,9 +144,6 @@ struct fk_ctx {
     int wslot_next = 0;
     hipEvent_t ev_upload_gate = nullptr;
     hipEvent_t ev_chunk[16] = {nullptr};      // fk_prove_r1cs, chunked hand-over: piece j of the witness has landed (spmv.hip)
-    // NTT / prover scratch
-    fk::DevBuf ntt_s1, ntt_s2, ntt_io, hbuf, sc_a, sc_b, scan_tmp, stage_a, stage_b, stage_c, stage_z, stage_d;
-    fk::DevBuf check;     // check.hip: the counters of an R1CS check, then the bitmap and the group flags the caller did not ask for
     // stats
     std::vector<fk::EventPair> ev_acc, ev_acc2, ev_ntt;   // G1 accumulate, G2 accumulate, NTT passes
     std::vector<hipEvent_t> ev_pool;
@@ -189,6 +201,61 @@ struct fk_key {
 #define FK_CAT2_(a, b) a##b
 #define FK_CAT_(a, b) FK_CAT2_(a, b)
 #define FK_RANGE(name) fk::RoctxRange FK_CAT_(fk_range_, __LINE__)(name)
+
+namespace fk {
+// ---- what a proof holds of its context BETWEEN two extern "C" calls (the one place that spells it)
+// The staging buffers stage_a/b/c and the lanes' sorts: an early front left the next submitted proof's a, b, c and witness sorts there
+// (spmv.hip: early_front) and fk_prove_r1cs_wait of that ticket picks them up.
+static inline bool proof_holds_staging(const fk_ctx *ctx) { return ctx->early.done; }
+// The MSM lanes: the above, or witness multiplications begun and not collected (fk_prove_msms_z_begin_dev .. _finish_dev) with whatever of
+// them is still deferred.  defer_back is set and cleared inside one call and deferred_tails is filled and drained together with deferred, so on
+// entry to a call the two add nothing to `deferred` -- unless an exception cut such a call short, and then refusing is right as well.
+static inline bool proof_holds_lanes(const fk_ctx *ctx) {
+    return proof_holds_staging(ctx) || ctx->wit_active || ctx->defer_back || !ctx->deferred.empty() || !ctx->deferred_tails.empty();
+}
+
+// The claim every entry point that borrows the staging buffers or the lanes opens with, in place of its hipSetDevice line: selects the
+// device, and refuses -- dropping nothing, the waiting ticket still gives its own proof -- while a submitted proof's early front holds them.
+// (The _dev entries of Poseidon and EdDSA touch only `misc`, which no proof uses between calls: they keep their plain hipSetDevice and
+// keep working during a front.)
+static inline int scratch_claim(fk_ctx *ctx, const char *who) {
+    if (proof_holds_staging(ctx)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: an early front of a submitted proof is outstanding (call fk_prove_r1cs_wait first)", who);
+    FK_HIP(ctx, hipSetDevice(ctx->device));
+    return FK_OK;
+}
+
+// Staging of a host-array entry, behind its claim: arrays are carved from a scratch buffer in the order they are asked for, each rounded
+// up to `align` bytes (16: rows of Fr / U256; 64 in verify.hip); the copies go on the main stream.
+struct HostStage {
+    fk_ctx *ctx;
+    size_t align = 16;
+    uint8_t *cur = nullptr;
+    size_t up(size_t bytes) const { return (bytes + align - 1) & ~(align - 1); }
+    // the arrays that follow come from `buf`, grown to hold all of them (+ slack)
+    int use(DevBuf &buf, std::initializer_list<size_t> sizes, size_t slack = 0) {
+        size_t sum = slack;
+        for (size_t b : sizes) sum += up(b);
+        FK_HIP(ctx, buf.reserve(sum));
+        cur = buf.as<uint8_t>();
+        return FK_OK;
+    }
+    template <class T> T *room(size_t bytes) { T *p = (T *)cur; cur += up(bytes); return p; }      // room for this many bytes out
+    template <class T> int in(const void *host, size_t bytes, T **d) {                             // this host array in: its device pointer
+        *d = room<T>(bytes);
+        if (bytes) FK_HIP(ctx, hipMemcpyAsync((void *)*d, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return FK_OK;
+    }
+    // the same for an array that has a buffer to itself
+    template <class T> int room(DevBuf &buf, size_t bytes, T **d) { FK_TRY(use(buf, {bytes})); *d = room<T>(bytes); return FK_OK; }
+    template <class T> int in(DevBuf &buf, const void *host, size_t bytes, T **d) { FK_TRY(use(buf, {bytes})); return in(host, bytes, d); }
+    // copy out; behind the last one, wait
+    int out(void *host, const void *d, size_t bytes, bool last = true) {
+        FK_HIP(ctx, hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (last) FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return FK_OK;
+    }
+};
+}  // namespace fk
 
 // Every extern "C" entry that can allocate on the host (std::vector / std::string / std::function behind almost all of them) runs
 // its body through this guard: a C++ exception must never leave an extern "C" function -- std::terminate would take the Rust or

@@ -490,22 +490,16 @@ static void sign_scalar(const uint64_t rho[4], const uint64_t h[4], const uint64
 }
 
 // ------------------------------------------------------------------------------------------ host drivers
-// device image: the error slot of the Poseidon calls (64 bytes), the curve record (512), the Poseidon table
+// device image (poseidon.hpp: misc_head): the flag slot, the curve record, the Poseidon table
 struct JjDev { const JjConst *c; const Fr *tab; };
-static constexpr size_t JJ_CONST_SLOT = 512;
 static_assert(sizeof(JjConst) <= JJ_CONST_SLOT, "the curve record outgrew its slot");
 
 static int jj_upload(fk_ctx *ctx, const fk_poseidon *h, JjDev *d) {
     std::string why;
     const JjConst *c = jj_consts(why);
     if (!c) FK_SET_ERR(ctx, FK_ERR_UNSUPPORTED, "%s", why.c_str());
-    const size_t tab_bytes = h ? h->tab.size() * sizeof(Fr) : 0;
-    FK_HIP(ctx, ctx->misc.reserve(64 + JJ_CONST_SLOT + tab_bytes));
-    uint8_t *base = (uint8_t *)ctx->misc.p;
-    FK_HIP(ctx, hipMemcpyAsync(base + 64, c, sizeof(JjConst), hipMemcpyHostToDevice, ctx->stream));
-    if (h) FK_HIP(ctx, hipMemcpyAsync(base + 64 + JJ_CONST_SLOT, h->tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d->c = (const JjConst *)(base + 64);
-    d->tab = (const Fr *)(base + 64 + JJ_CONST_SLOT);
+    PosDev m; FK_TRY(misc_head(ctx, h, c, sizeof(JjConst), &m));
+    *d = JjDev{(const JjConst *)m.curve, m.tab};
     return FK_OK;
 }
 
@@ -567,19 +561,17 @@ int fk_jubjub_mul_batch(fk_ctx *ctx, const uint64_t *points, const uint64_t *sca
     if (!scalars || !out) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     if (n > JJ_MAX_BATCH) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "jubjub: batch too large");
     if (points) FK_TRY(check_fr_rows(ctx, points, 2 * n, "jubjub mul: point coordinate"));
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "jubjub mul"));
     const size_t pb = 2 * n * sizeof(Fr), sb = n * sizeof(U256);
-    FK_HIP(ctx, ctx->stage_a.reserve(pb)); FK_HIP(ctx, ctx->stage_b.reserve(sb)); FK_HIP(ctx, ctx->stage_c.reserve(pb));
-    if (points) FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, points, pb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, scalars, sb, hipMemcpyHostToDevice, ctx->stream));
+    HostStage st{ctx};
+    const Fr *d_pts = nullptr; const U256 *d_sc; Fr *d_out;
+    if (points) FK_TRY(st.in(ctx->stage_a, points, pb, &d_pts));
+    FK_TRY(st.in(ctx->stage_b, scalars, sb, &d_sc)); FK_TRY(st.room(ctx->stage_c, pb, &d_out));
     JjDev d; FK_TRY(jj_upload(ctx, nullptr, &d));
-    hipLaunchKernelGGL(jubjub_mul_kernel, dim3(jj_blocks(n)), dim3(JJ_THREADS), 0, ctx->stream, d.c, points ? ctx->stage_a.as<Fr>() : (const Fr *)nullptr,
-                       (const U256 *)ctx->stage_b.p, n, ctx->stage_c.as<Fr>());
+    hipLaunchKernelGGL(jubjub_mul_kernel, dim3(jj_blocks(n)), dim3(JJ_THREADS), 0, ctx->stream, d.c, d_pts, d_sc, n, d_out);
     FK_HIP(ctx, hipGetLastError());
     FK_DBG(ctx, "jubjub_mul_kernel");
-    FK_HIP(ctx, hipMemcpyAsync(out, ctx->stage_c.p, pb, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    return st.out(out, d_out, pb);
 }); }
 
 int fk_jubjub_decompress_batch(fk_ctx *ctx, const uint64_t *x, size_t n, uint64_t *y, uint8_t *ok) { return fk_guard(ctx, [&]() -> int {
@@ -588,19 +580,17 @@ int fk_jubjub_decompress_batch(fk_ctx *ctx, const uint64_t *x, size_t n, uint64_
     if (!x || !y || !ok) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     if (n > JJ_MAX_BATCH) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "jubjub: batch too large");
     FK_TRY(check_fr_rows(ctx, x, n, "jubjub decompress: x"));
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "jubjub decompress"));
     const size_t xb = n * sizeof(Fr);
-    FK_HIP(ctx, ctx->stage_a.reserve(xb)); FK_HIP(ctx, ctx->stage_b.reserve(xb)); FK_HIP(ctx, ctx->stage_c.reserve(n));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, x, xb, hipMemcpyHostToDevice, ctx->stream));
+    HostStage st{ctx};
+    const Fr *d_x; Fr *d_y; uint8_t *d_ok;
+    FK_TRY(st.in(ctx->stage_a, x, xb, &d_x)); FK_TRY(st.room(ctx->stage_b, xb, &d_y)); FK_TRY(st.room(ctx->stage_c, n, &d_ok));
     JjDev d; FK_TRY(jj_upload(ctx, nullptr, &d));
-    hipLaunchKernelGGL(jubjub_decompress_kernel, dim3(jj_blocks(n)), dim3(JJ_THREADS), 0, ctx->stream, d.c, ctx->stage_a.as<Fr>(), n, ctx->stage_b.as<Fr>(),
-                       ctx->stage_c.as<uint8_t>());
+    hipLaunchKernelGGL(jubjub_decompress_kernel, dim3(jj_blocks(n)), dim3(JJ_THREADS), 0, ctx->stream, d.c, d_x, n, d_y, d_ok);
     FK_HIP(ctx, hipGetLastError());
     FK_DBG(ctx, "jubjub_decompress_kernel");
-    FK_HIP(ctx, hipMemcpyAsync(y, ctx->stage_b.p, xb, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(ok, ctx->stage_c.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    FK_TRY(st.out(y, d_y, xb, false));
+    return st.out(ok, d_ok, n);
 }); }
 
 int fk_eddsa_sign_batch(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *sk, const uint64_t *m, const uint64_t *rho, size_t n, uint64_t *s, uint64_t *r_x,
@@ -623,23 +613,21 @@ int fk_eddsa_sign_batch(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *sk, c
         for (size_t i = 0; i < n; i++) hash_r(c, sk + 4 * i, fr_from_limbs(m + 4 * i), own_rho.data() + 4 * i);
         rho = own_rho.data();
     }
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "eddsa sign"));
     const size_t eb = n * 32;
-    FK_HIP(ctx, ctx->stage_a.reserve(3 * eb)); FK_HIP(ctx, ctx->stage_b.reserve(3 * eb));
-    uint8_t *in = ctx->stage_a.as<uint8_t>(), *res = ctx->stage_b.as<uint8_t>();
-    FK_HIP(ctx, hipMemcpyAsync(in, sk, eb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(in + eb, rho, eb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(in + 2 * eb, m, eb, hipMemcpyHostToDevice, ctx->stream));
+    HostStage st{ctx};
+    const U256 *d_sk, *d_rho; const Fr *d_m;
+    FK_TRY(st.use(ctx->stage_a, {eb, eb, eb})); FK_TRY(st.in(sk, eb, &d_sk)); FK_TRY(st.in(rho, eb, &d_rho)); FK_TRY(st.in(m, eb, &d_m));
+    FK_TRY(st.use(ctx->stage_b, {eb, eb, eb}));
+    Fr *d_rx = st.room<Fr>(eb), *d_ax = st.room<Fr>(eb); U256 *d_h = st.room<U256>(eb);
     JjDev d; FK_TRY(jj_upload(ctx, h, &d));
-    hipLaunchKernelGGL(eddsa_sign_points_kernel, dim3(jj_blocks(n)), dim3(JJ_THREADS), 0, ctx->stream, d.c, d.tab, h->f, h->p, (const U256 *)in, (const U256 *)(in + eb),
-                       (const Fr *)(in + 2 * eb), n, (Fr *)res, (Fr *)(res + eb), (U256 *)(res + 2 * eb));
+    hipLaunchKernelGGL(eddsa_sign_points_kernel, dim3(jj_blocks(n)), dim3(JJ_THREADS), 0, ctx->stream, d.c, d.tab, h->f, h->p, d_sk, d_rho, d_m, n, d_rx, d_ax, d_h);
     FK_HIP(ctx, hipGetLastError());
     FK_DBG(ctx, "eddsa_sign_points_kernel");
     std::vector<uint64_t> hs(4 * n);
-    if (r_x) FK_HIP(ctx, hipMemcpyAsync(r_x, res, eb, hipMemcpyDeviceToHost, ctx->stream));
-    if (a_x) FK_HIP(ctx, hipMemcpyAsync(a_x, res + eb, eb, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(hs.data(), res + 2 * eb, eb, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (r_x) FK_TRY(st.out(r_x, d_rx, eb, false));
+    if (a_x) FK_TRY(st.out(a_x, d_ax, eb, false));
+    FK_TRY(st.out(hs.data(), d_h, eb));
     for (size_t i = 0; i < n; i++) sign_scalar(rho + 4 * i, hs.data() + 4 * i, sk + 4 * i, s + 4 * i);
     return FK_OK;
 }); }
@@ -660,18 +648,15 @@ int fk_eddsa_verify_batch(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *s, 
     FK_TRY(eddsa_args(ctx, h, n));
     if (!n) return FK_OK;
     if (!s || !r || !a || !m || !accept) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "eddsa verify"));
     const size_t eb = n * 32;
-    FK_HIP(ctx, ctx->stage_a.reserve(4 * eb)); FK_HIP(ctx, ctx->stage_b.reserve(n));
-    uint8_t *in = ctx->stage_a.as<uint8_t>();
-    FK_HIP(ctx, hipMemcpyAsync(in, s, eb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(in + eb, r, eb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(in + 2 * eb, a, eb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(in + 3 * eb, m, eb, hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(verify_dev(ctx, h, in, in + eb, in + 2 * eb, in + 3 * eb, n, ctx->stage_b.p));
-    FK_HIP(ctx, hipMemcpyAsync(accept, ctx->stage_b.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    const void *d_s, *d_r, *d_a, *d_m; uint8_t *d_accept;
+    FK_TRY(st.use(ctx->stage_a, {eb, eb, eb, eb}));
+    FK_TRY(st.in(s, eb, &d_s)); FK_TRY(st.in(r, eb, &d_r)); FK_TRY(st.in(a, eb, &d_a)); FK_TRY(st.in(m, eb, &d_m));
+    FK_TRY(st.room(ctx->stage_b, n, &d_accept));
+    FK_TRY(verify_dev(ctx, h, d_s, d_r, d_a, d_m, n, d_accept));
+    return st.out(accept, d_accept, n);
 }); }
 
 }  // extern "C"

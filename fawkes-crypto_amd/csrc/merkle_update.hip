@@ -213,7 +213,7 @@ int fk_poseidon_merkle_update_timed_dev(fk_ctx *ctx, const fk_poseidon *h, void 
     if (ms) ms[0] = ms[1] = 0;
     if (!k) return FK_OK;
     if (!d_nodes || !d_indices || !d_new_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "merkle update"));      // update_dev sorts in stage_a/b/c
     return update_dev(ctx, h, (Fr *)d_nodes, depth, (const uint64_t *)d_indices, (const Fr *)d_new_leaves, (uint32_t)k, (Fr *)d_old_leaves, (Fr *)d_siblings,
                       (Fr *)d_roots, ms);
 }); }
@@ -229,7 +229,7 @@ int fk_poseidon_merkle_update(fk_ctx *ctx, const fk_poseidon *h, void *d_nodes, 
     FK_TRY(update_args(ctx, h, depth, k));
     if (!k) return FK_OK;
     if (!d_nodes || !indices || !new_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "merkle update"));
     // one block: new leaves | old leaves | roots | siblings | indices (the outputs are used only where asked for)
     const size_t ib = k * sizeof(uint64_t), lb = k * sizeof(Fr), sb = siblings ? lb * depth : 0;
     MuDevBlock blk;

@@ -1409,8 +1409,7 @@ static int msm_front_dump(fk_ctx *ctx, const Fr *d_scalars, size_t n, bool merge
                           uint32_t *perm, fk_msm_dyn_info *dyn_out, uint32_t *tasks, size_t tasks_cap, uint32_t *obs, size_t obs_cap) {
     if (n == 0) return FK_OK;
     if (n >= ((size_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: n too large");
-    if (ctx->defer_back || !ctx->deferred.empty() || !ctx->deferred_tails.empty() || ctx->wit_active || ctx->early.done)
-        FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm front dump: a proof is in flight on this context");
+    if (proof_holds_lanes(ctx)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm front dump: a proof is in flight on this context");
     int ti = -1;
     for (int i = 0; i < MSM_TAILS; i++) if (!ctx->tails[i].active) { ti = i; break; }
     if (ti < 0) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: too many outstanding multiplications");

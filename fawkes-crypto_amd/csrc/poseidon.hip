@@ -236,14 +236,13 @@ int fk_poseidon_hash_batch(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *in
     if (n_inputs == 0 || n_inputs >= h->t) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "poseidon: 0 < n_inputs < t required (n_inputs = %u, t = %u)", n_inputs, h->t);
     if (!n) return FK_OK;
     if (!inputs || !out) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "poseidon hash"));
     const size_t in_bytes = n * n_inputs * sizeof(Fr), out_bytes = n * sizeof(Fr);
-    FK_HIP(ctx, ctx->stage_a.reserve(in_bytes)); FK_HIP(ctx, ctx->stage_b.reserve(out_bytes));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, inputs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(hash_batch_dev(ctx, h, ctx->stage_a.as<Fr>(), n_inputs, n, ctx->stage_b.as<Fr>()));
-    FK_HIP(ctx, hipMemcpyAsync(out, ctx->stage_b.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    const Fr *d_in; Fr *d_out;
+    FK_TRY(st.in(ctx->stage_a, inputs, in_bytes, &d_in)); FK_TRY(st.room(ctx->stage_b, out_bytes, &d_out));
+    FK_TRY(hash_batch_dev(ctx, h, d_in, n_inputs, n, d_out));
+    return st.out(out, d_out, out_bytes);
 }); }
 
 int fk_poseidon_sponge_batch(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *inputs, uint64_t len, size_t n, uint64_t *out) { return fk_guard(ctx, [&]() -> int {
@@ -252,14 +251,13 @@ int fk_poseidon_sponge_batch(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *
     if (!n) return FK_OK;
     if (!out || (len && !inputs)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     if (len > ((uint64_t)1 << 40) / n) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "poseidon: sponge batch too large");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "poseidon sponge"));
     const size_t in_bytes = n * len * sizeof(Fr), out_bytes = n * sizeof(Fr);
-    FK_HIP(ctx, ctx->stage_a.reserve(in_bytes + sizeof(Fr))); FK_HIP(ctx, ctx->stage_b.reserve(out_bytes));
-    if (in_bytes) FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, inputs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(sponge_batch_dev(ctx, h, ctx->stage_a.as<Fr>(), len, n, ctx->stage_b.as<Fr>()));
-    FK_HIP(ctx, hipMemcpyAsync(out, ctx->stage_b.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    const Fr *d_in; Fr *d_out;
+    FK_TRY(st.use(ctx->stage_a, {in_bytes}, sizeof(Fr))); FK_TRY(st.in(inputs, in_bytes, &d_in)); FK_TRY(st.room(ctx->stage_b, out_bytes, &d_out));
+    FK_TRY(sponge_batch_dev(ctx, h, d_in, len, n, d_out));
+    return st.out(out, d_out, out_bytes);
 }); }
 
 // ------------------------------------------------------------------------------------------ Merkle trees
@@ -278,14 +276,13 @@ int fk_poseidon_merkle_root(fk_ctx *ctx, const fk_poseidon *h, const uint64_t *l
     uint32_t L = 0;
     FK_TRY(tree_args(ctx, h, n_leaves, &L));
     if (!leaves || !out_root) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "merkle root"));
     const uint64_t total = ((uint64_t)2 << L) - 1;
-    FK_HIP(ctx, ctx->stage_a.reserve(total * sizeof(Fr)));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, leaves, n_leaves * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(merkle_tree_dev(ctx, h, ctx->stage_a.as<Fr>(), n_leaves, L));
-    FK_HIP(ctx, hipMemcpyAsync(out_root, ctx->stage_a.as<Fr>() + (total - 1), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    Fr *d_nodes;
+    FK_TRY(st.use(ctx->stage_a, {total * sizeof(Fr)})); FK_TRY(st.in(leaves, n_leaves * sizeof(Fr), &d_nodes));      // the leaves at the head of the node array
+    FK_TRY(merkle_tree_dev(ctx, h, d_nodes, n_leaves, L));
+    return st.out(out_root, d_nodes + (total - 1), sizeof(Fr));
 }); }
 
 int fk_poseidon_merkle_proofs_dev(fk_ctx *ctx, const void *d_nodes, uint32_t depth, const void *d_indices, size_t n, void *d_siblings) { return fk_guard(ctx, [&]() -> int {
@@ -294,9 +291,9 @@ int fk_poseidon_merkle_proofs_dev(fk_ctx *ctx, const void *d_nodes, uint32_t dep
     if (!n) return FK_OK;
     if (!d_nodes || !d_indices) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     if (n > ((size_t)1 << 36)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "merkle: too many proofs");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
-    FK_HIP(ctx, ctx->misc.reserve(64));
-    uint32_t *flag = ctx->misc.as<uint32_t>();
+    FK_HIP(ctx, hipSetDevice(ctx->device));       // misc only: runs beside an early front
+    PosDev m; FK_TRY(misc_head(ctx, nullptr, nullptr, 0, &m));
+    uint32_t *flag = m.flag;
     if (depth == 0) {       // no siblings to gather: only the indices are checked (all must be 0), on the host side of a small copy
         std::vector<uint64_t> idx(n);
         FK_HIP(ctx, hipMemcpyAsync(idx.data(), d_indices, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -342,16 +339,14 @@ int fk_poseidon_merkle_proof_roots(fk_ctx *ctx, const fk_poseidon *h, const uint
     if (!leaves || !out || (depth && (!siblings || !indices))) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     if (depth == 0) { memmove(out, leaves, n * sizeof(Fr)); return FK_OK; }
     if (n > ((size_t)1 << 34)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "merkle: too many proofs");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "merkle proof roots"));
     const size_t lb = n * sizeof(Fr), sb = n * depth * sizeof(Fr), ib = n * sizeof(uint64_t);
-    FK_HIP(ctx, ctx->stage_a.reserve(lb)); FK_HIP(ctx, ctx->stage_b.reserve(sb)); FK_HIP(ctx, ctx->stage_c.reserve(ib)); FK_HIP(ctx, ctx->stage_d.reserve(lb));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, leaves, lb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, siblings, sb, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_c.p, indices, ib, hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(proof_roots_dev(ctx, h, ctx->stage_a.as<Fr>(), ctx->stage_b.as<Fr>(), ctx->stage_c.as<uint64_t>(), depth, n, ctx->stage_d.as<Fr>()));
-    FK_HIP(ctx, hipMemcpyAsync(out, ctx->stage_d.p, lb, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    const Fr *d_leaves, *d_sib; const uint64_t *d_idx; Fr *d_out;
+    FK_TRY(st.in(ctx->stage_a, leaves, lb, &d_leaves)); FK_TRY(st.in(ctx->stage_b, siblings, sb, &d_sib)); FK_TRY(st.in(ctx->stage_c, indices, ib, &d_idx));
+    FK_TRY(st.room(ctx->stage_d, lb, &d_out));
+    FK_TRY(proof_roots_dev(ctx, h, d_leaves, d_sib, d_idx, depth, n, d_out));
+    return st.out(out, d_out, lb);
 }); }
 
 }  // extern "C"

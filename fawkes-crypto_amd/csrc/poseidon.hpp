@@ -195,17 +195,22 @@ static inline void fr_to_limbs(const Fr &a, uint64_t *l) { for (int i = 0; i < 4
 static inline int dims_ok(uint32_t t, uint32_t f, uint32_t p) { return t >= 2 && t <= POS_MAX_T && (uint64_t)f + p != 0 && (uint64_t)f + p <= 4096; }
 
 // ------------------------------------------------------------------------------------------ host drivers
-// the parameters travel with every call: <= 20 KB at the head of ctx->misc, behind a 64-byte slot for the error flag of the sibling gather
-struct PosDev { const Fr *tab; uint32_t *flag; };
+// The head of ctx->misc, as every hashing and signature call lays it out: a slot for the error flag (sibling gather, update's index check) |
+// with a curve record: its slot (eddsa.hip) | the Poseidon table.  The parameters travel with every call: <= 20 KB.
+static constexpr size_t MISC_FLAG_SLOT = 64, JJ_CONST_SLOT = 512;
+struct PosDev { const Fr *tab; uint32_t *flag; const void *curve; };
 
-static int pos_upload(fk_ctx *ctx, const fk_poseidon *h, PosDev *d) {
-    const size_t bytes = h->tab.size() * sizeof(Fr);
-    FK_HIP(ctx, ctx->misc.reserve(64 + bytes));
-    FK_HIP(ctx, hipMemcpyAsync((uint8_t *)ctx->misc.p + 64, h->tab.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    d->tab = (const Fr *)((uint8_t *)ctx->misc.p + 64);
-    d->flag = ctx->misc.as<uint32_t>();
+// h, curve: what to upload (either may be null; without a curve record the table follows the flag slot at once)
+static int misc_head(fk_ctx *ctx, const fk_poseidon *h, const void *curve, size_t curve_bytes, PosDev *d) {
+    const size_t tab_off = MISC_FLAG_SLOT + (curve ? JJ_CONST_SLOT : 0), tab_bytes = h ? h->tab.size() * sizeof(Fr) : 0;
+    FK_HIP(ctx, ctx->misc.reserve(tab_off + tab_bytes));
+    uint8_t *base = ctx->misc.as<uint8_t>();
+    if (curve) FK_HIP(ctx, hipMemcpyAsync(base + MISC_FLAG_SLOT, curve, curve_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (h) FK_HIP(ctx, hipMemcpyAsync(base + tab_off, h->tab.data(), tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d = PosDev{(const Fr *)(base + tab_off), (uint32_t *)base, base + MISC_FLAG_SLOT};
     return FK_OK;
 }
+static int pos_upload(fk_ctx *ctx, const fk_poseidon *h, PosDev *d) { return misc_head(ctx, h, nullptr, 0, d); }
 
 static inline unsigned pos_blocks(size_t n) { return (unsigned)((n + POS_THREADS - 1) / POS_THREADS); }
 

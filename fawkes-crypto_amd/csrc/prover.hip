@@ -119,10 +119,7 @@ void fk_free(fk_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     ntt_free_domains(ctx);
     msm_release(ctx);
-    for (DevBuf *b : {&ctx->misc, &ctx->ntt_s1, &ctx->ntt_s2, &ctx->ntt_io,
-                      &ctx->hbuf, &ctx->sc_a, &ctx->sc_b, &ctx->scan_tmp, &ctx->stage_a, &ctx->stage_b, &ctx->stage_c,
-                      &ctx->stage_z, &ctx->stage_d, &ctx->check})
-        b->release();
+    ctx->release_scratch();
     for (auto &v : {&ctx->ev_acc, &ctx->ev_acc2, &ctx->ev_ntt}) for (auto &ep : *v) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->copy_st) { (void)hipStreamSynchronize(ctx->copy_st); (void)hipStreamDestroy(ctx->copy_st); }
@@ -142,16 +139,14 @@ int fk_trim(fk_ctx *ctx) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     FK_HIP(ctx, hipSetDevice(ctx->device));
     for (const auto &w : ctx->wslot) if (w.pending) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "trim: a submitted proof is outstanding (call fk_prove_r1cs_wait first)");
-    if (ctx->wit_active || ctx->early.done || !ctx->deferred.empty()) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "trim: multiplications are in flight");
+    if (proof_holds_lanes(ctx)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "trim: multiplications are in flight");
     for (const auto &t : ctx->tails) if (t.active) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "trim: a multiplication begun with a *_begin_* call has not been collected");
     FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     FK_TRY(msm_sync(ctx));
     if (ctx->copy_st) FK_HIP(ctx, hipStreamSynchronize(ctx->copy_st));
     ntt_free_domains(ctx);
     msm_release(ctx);
-    for (DevBuf *b : {&ctx->misc, &ctx->ntt_s1, &ctx->ntt_s2, &ctx->ntt_io, &ctx->hbuf, &ctx->sc_a, &ctx->sc_b, &ctx->scan_tmp, &ctx->stage_a, &ctx->stage_b,
-                      &ctx->stage_c, &ctx->stage_z, &ctx->stage_d, &ctx->check})
-        b->release();
+    ctx->release_scratch();
     for (auto &w : ctx->wslot) { w.buf.release(); w.deferred = false; if (w.ready) { (void)hipEventDestroy(w.ready); w.ready = nullptr; } if (w.part) { (void)hipEventDestroy(w.part); w.part = nullptr; } }      // "holds nothing" again
     ctx->lane_prev = 0; ctx->lane_next = 0;
     FK_TRY(streams_init(ctx));      // the streams come back together, in the same order
@@ -764,7 +759,7 @@ int fk_prove_msms_z_dev(fk_ctx *ctx, const fk_key *key, const void *d_z, const v
 int fk_prove_msm_h_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_G1_BYTES]) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!key || !out || (!d_h_slice && key->h_hi > key->h_lo)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "msm over the h array"));
     G1Xyzz H;
     FK_TRY(msm_g1_dev(ctx, key->d_h, (const Fr *)d_h_slice, key->h_hi - key->h_lo, &H, &key->pre_h));
     g1_to_raw(out, H);
@@ -774,7 +769,7 @@ int fk_prove_msm_h_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, ui
 int fk_prove_msm_array_dev(fk_ctx *ctx, const fk_key *key, int which, const void *d_scalars, uint8_t *out) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!key || !out || which < FK_ARRAY_H || which > FK_ARRAY_B_G2) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm over a key array: null argument or unknown array");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "msm over a key array"));
     const uint64_t n = which == FK_ARRAY_H ? key->h_hi - key->h_lo : which == FK_ARRAY_L ? key->l_hi - key->l_lo
                      : which == FK_ARRAY_A ? key->a_hi - key->a_lo : which == FK_ARRAY_B_G1 ? key->b_hi - key->b_lo : key->b2_hi - key->b2_lo;
     if (!d_scalars && n) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm over a key array: null scalars");
@@ -930,15 +925,13 @@ int fk_fr_mul_batch(fk_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t 
     if (!ctx) return FK_ERR_BAD_ARG;
     if (n && (!a || !b || !out)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     if (!n) return FK_OK;
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "fr_mul_batch"));
     const size_t bytes = n * sizeof(Fr);
-    FK_HIP(ctx, ctx->stage_a.reserve(bytes)); FK_HIP(ctx, ctx->stage_b.reserve(bytes));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, a, bytes, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, b, bytes, hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(fr_mul_batch_dev(ctx, ctx->stage_a.as<Fr>(), ctx->stage_b.as<Fr>(), ctx->stage_a.as<Fr>(), n));
-    FK_HIP(ctx, hipMemcpyAsync(out, ctx->stage_a.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    Fr *d_a, *d_b;
+    FK_TRY(st.in(ctx->stage_a, a, bytes, &d_a)); FK_TRY(st.in(ctx->stage_b, b, bytes, &d_b));
+    FK_TRY(fr_mul_batch_dev(ctx, d_a, d_b, d_a, n));
+    return st.out(out, d_a, bytes);
 }); }
 
 int fk_ntt_dev(fk_ctx *ctx, void *d_data, uint32_t log_n, int inverse, int coset) { return fk_guard(ctx, [&]() -> int {
@@ -1005,7 +998,7 @@ int fk_quotient_h(fk_ctx *ctx, const uint64_t *a, const uint64_t *b, const uint6
     if (!a || !b || !c || !h_out || !n) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     const uint32_t log_n = ceil_log2_u64(n);
     if (log_n >= FK_FR_S) FK_SET_ERR(ctx, FK_ERR_DOMAIN_TOO_LARGE, "evaluation domain 2^%u too large (max 2^%d)", log_n, FK_FR_S - 1);
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "quotient_h"));
     const size_t mb = sizeof(Fr) << log_n, nb = n * sizeof(Fr);
     FK_HIP(ctx, ctx->stage_a.reserve(mb)); FK_HIP(ctx, ctx->stage_b.reserve(mb)); FK_HIP(ctx, ctx->stage_c.reserve(mb));
     FK_HIP(ctx, ctx->hbuf.reserve(mb));
@@ -1021,7 +1014,7 @@ int fk_quotient_h(fk_ctx *ctx, const uint64_t *a, const uint64_t *b, const uint6
 int fk_msm_g1_dev(fk_ctx *ctx, const void *d_bases, const void *d_scalars, size_t n, uint8_t out[FK_G1_BYTES]) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!out || (n && (!d_bases || !d_scalars))) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "msm"));
     G1Xyzz r;
     FK_TRY(msm_g1_dev(ctx, (const G1Affine *)d_bases, (const Fr *)d_scalars, n, &r));
     g1_to_raw(out, r);
@@ -1030,7 +1023,7 @@ int fk_msm_g1_dev(fk_ctx *ctx, const void *d_bases, const void *d_scalars, size_
 int fk_msm_g2_dev(fk_ctx *ctx, const void *d_bases, const void *d_scalars, size_t n, uint8_t out[FK_G2_BYTES]) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!out || (n && (!d_bases || !d_scalars))) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "msm"));
     G2Xyzz r;
     FK_TRY(msm_g2_dev(ctx, (const G2Affine *)d_bases, (const Fr *)d_scalars, n, &r));
     g2_to_raw(out, r);
@@ -1039,13 +1032,12 @@ int fk_msm_g2_dev(fk_ctx *ctx, const void *d_bases, const void *d_scalars, size_
 
 static int msm_host(fk_ctx *ctx, const uint8_t *bases, const uint64_t *scalars, size_t n, size_t w, uint8_t *out) {
     if (!out || (n && (!bases || !scalars))) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
-    FK_HIP(ctx, ctx->stage_a.reserve(n * w + 16)); FK_HIP(ctx, ctx->stage_z.reserve(n * sizeof(Fr) + 16));
-    if (n) {
-        FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, bases, n * w, hipMemcpyHostToDevice, ctx->stream));
-        FK_HIP(ctx, hipMemcpyAsync(ctx->stage_z.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    }
-    return w == 64 ? fk_msm_g1_dev(ctx, ctx->stage_a.p, ctx->stage_z.p, n, out) : fk_msm_g2_dev(ctx, ctx->stage_a.p, ctx->stage_z.p, n, out);
+    FK_TRY(scratch_claim(ctx, "msm"));
+    HostStage st{ctx};
+    void *d_bases, *d_scalars;
+    FK_TRY(st.use(ctx->stage_a, {n * w}, 16)); FK_TRY(st.in(bases, n * w, &d_bases));
+    FK_TRY(st.use(ctx->stage_z, {n * sizeof(Fr)}, 16)); FK_TRY(st.in(scalars, n * sizeof(Fr), &d_scalars));
+    return w == 64 ? fk_msm_g1_dev(ctx, d_bases, d_scalars, n, out) : fk_msm_g2_dev(ctx, d_bases, d_scalars, n, out);
 }
 int fk_msm_g1(fk_ctx *ctx, const uint8_t *bases, const uint64_t *scalars, size_t n, uint8_t out[FK_G1_BYTES]) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;

@@ -78,21 +78,17 @@ int fk_verify_batch_dev(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uin
     if (!count) return FK_OK;
     uint32_t n_ic = 0;
     FK_TRY(vk_check(ctx, vk, vk_len, n_inputs, &n_ic));
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "verify"));
     const size_t in_b = (size_t)count * n_inputs * 32, pr_b = (size_t)count * FK_PROOF_BYTES;
-    const size_t vk_al = (vk_len + 63) & ~(size_t)63, in_al = (in_b + 63) & ~(size_t)63;
-    FK_HIP(ctx, ctx->misc.reserve(vk_al + in_al + pr_b + 64));
-    FK_HIP(ctx, ctx->stage_d.reserve(count + 64));
-    uint8_t *d_vk = ctx->misc.as<uint8_t>(), *d_in = d_vk + vk_al, *d_pr = d_in + in_al;
-    int8_t *d_out = ctx->stage_d.as<int8_t>();
-    FK_HIP(ctx, hipMemcpyAsync(d_vk, vk, vk_len, hipMemcpyHostToDevice, ctx->stream));
-    if (in_b) FK_HIP(ctx, hipMemcpyAsync(d_in, inputs, in_b, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(d_pr, proofs, pr_b, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(verify_batch_kernel, dim3((count + 63) / 64), dim3(64), 0, ctx->stream, d_vk, n_ic, (const FrC *)d_in, d_pr, count, d_out);
+    HostStage st{ctx, 64};
+    const uint8_t *d_vk, *d_pr; const FrC *d_in; int8_t *d_out;
+    FK_TRY(st.use(ctx->misc, {vk_len, in_b, pr_b}, 64));
+    FK_TRY(st.in(vk, vk_len, &d_vk)); FK_TRY(st.in(inputs, in_b, &d_in)); FK_TRY(st.in(proofs, pr_b, &d_pr));
+    FK_TRY(st.use(ctx->stage_d, {count}, 64)); d_out = st.room<int8_t>(count);
+    hipLaunchKernelGGL(verify_batch_kernel, dim3((count + 63) / 64), dim3(64), 0, ctx->stream, d_vk, n_ic, d_in, d_pr, count, d_out);
     FK_HIP(ctx, hipGetLastError());
     std::vector<int8_t> res(count);
-    FK_HIP(ctx, hipMemcpyAsync(res.data(), d_out, count, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    FK_TRY(st.out(res.data(), d_out, count));
     // A proof that does not decode (a coordinate >= q: upstream fails in `Proof`'s Borsh reader, before verify is reached) is
     // that proof's rejection, not the batch's failure -- one bad submission must not hide the verdicts on the others.
     uint32_t n_bad = 0, first_bad = 0;

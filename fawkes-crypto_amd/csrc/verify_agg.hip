@@ -136,7 +136,7 @@ static int front_host(const uint8_t *proofs, uint32_t count, const uint64_t *w, 
 }
 
 static int front_dev(fk_ctx *ctx, const uint8_t *proofs, uint32_t count, const uint64_t *w, AggFront &o) {
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "verify_aggregate"));
     const size_t pr_b = (size_t)count * FK_PROOF_BYTES, w_b = (size_t)count * 16, lev = level_total(count);
     FK_HIP(ctx, ctx->misc.reserve(pr_b + w_b));
     FK_HIP(ctx, ctx->stage_a.reserve((size_t)count * sizeof(Affine<FqC>)));

@@ -346,14 +346,13 @@ int fk_witness_generate(fk_ctx *ctx, const fk_witness_prog *prog, const uint64_t
     if (!z || (prog->n_given && !given)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     const uint64_t len = witness_len(prog, copies);
     if (!len) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "witness: %u copies of this program do not fit 32-bit variable indices", copies);
-    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_TRY(scratch_claim(ctx, "witness"));
     const size_t gb = (size_t)copies * prog->n_given * sizeof(Fr), zb = (size_t)len * sizeof(Fr);
-    FK_HIP(ctx, ctx->stage_a.reserve(gb ? gb : sizeof(Fr))); FK_HIP(ctx, ctx->stage_b.reserve(zb));
-    if (gb) FK_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, given, gb, hipMemcpyHostToDevice, ctx->stream));
-    FK_TRY(witness_run(ctx, prog, ctx->stage_a.p, copies, ctx->stage_b.p));
-    FK_HIP(ctx, hipMemcpyAsync(z, ctx->stage_b.p, zb, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FK_OK;
+    HostStage st{ctx};
+    const void *d_given; void *d_z;
+    FK_TRY(st.use(ctx->stage_a, {gb}, gb ? 0 : sizeof(Fr))); FK_TRY(st.in(given, gb, &d_given)); FK_TRY(st.room(ctx->stage_b, zb, &d_z));
+    FK_TRY(witness_run(ctx, prog, d_given, copies, d_z));
+    return st.out(z, d_z, zb);
 }); }
 
 }  // extern "C"

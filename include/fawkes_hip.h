@@ -217,6 +217,7 @@ int fk_prove_msms_dev(fk_ctx *ctx, const fk_key *key, void *d_a, void *d_b, void
 int fk_prove_msms_z_dev(fk_ctx *ctx, const fk_key *key, const void *d_z, const void *d_a_aux_density,
                         const void *d_b_input_density, const void *d_b_aux_density,
                         uint8_t out_msms[FK_MSM_RESULT_BYTES], fk_timings *timings);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_prove_msm_h_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_G1_BYTES]);
 /* ONE multiplication over one of the key's resident arrays, alone (bench / test micro entry point like fk_msm_g1, SURVEY 8(b);
  * bellman's `multiexp(worker, (bases, 0), FullDensity, scalars)` over that array): `which` = FK_ARRAY_H / _L / _A / _B_G1 / _B_G2,
@@ -227,6 +228,7 @@ int fk_prove_msm_h_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, ui
 #define FK_ARRAY_A 2
 #define FK_ARRAY_B_G1 3
 #define FK_ARRAY_B_G2 4
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_prove_msm_array_dev(fk_ctx *ctx, const fk_key *key, int which, const void *d_scalars, uint8_t *out);
 /* Split form for schedules that compute the quotient while the witness multiplications run: _begin queues L, A, B1, B2
  * of this key's slices on the library's MSM streams (nothing is put on the main stream, so fk_quotient_h_dev / fk_dq_*
@@ -282,19 +284,25 @@ int fk_dq_cross_sub_dev(fk_ctx *ctx, void *d_buf, const void *d_sub, uint32_t lo
 
 /* ---------------------------------------------------------------- building blocks (tests / benches)
  * bellman_ce::domain::EvaluationDomain pieces. */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_fr_mul_batch(fk_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
 /* in-place natural-order NTT of 2^log_n elements; inverse: omega^-1 and 1/n; coset: bellman's
  * coset_fft / icoset_fft (multiplicative generator 7). */
 int fk_ntt(fk_ctx *ctx, uint64_t *data, uint32_t log_n, int inverse, int coset);
 int fk_ntt_dev(fk_ctx *ctx, void *d_data, uint32_t log_n, int inverse, int coset);
 /* h = (A*B - C)/Z coefficients: out has m-1 elements, m = next_pow2(n). */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_quotient_h(fk_ctx *ctx, const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n,
                   uint64_t *h_out);
 int fk_quotient_h_dev(fk_ctx *ctx, void *d_a, void *d_b, void *d_c, uint64_t n, void *d_h_out /* m x 32 B */);
 /* bellman_ce::multiexp (App. A.3): sum_i scalars[i] * bases[i]; scalars Montgomery Fr; out raw affine. */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_msm_g1(fk_ctx *ctx, const uint8_t *bases, const uint64_t *scalars, size_t n, uint8_t out[FK_G1_BYTES]);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_msm_g2(fk_ctx *ctx, const uint8_t *bases, const uint64_t *scalars, size_t n, uint8_t out[FK_G2_BYTES]);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_msm_g1_dev(fk_ctx *ctx, const void *d_bases, const void *d_scalars, size_t n, uint8_t out[FK_G1_BYTES]);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_msm_g2_dev(fk_ctx *ctx, const void *d_bases, const void *d_scalars, size_t n, uint8_t out[FK_G2_BYTES]);
 /* n valid pseudo-random curve points written to device memory (bench/test input generator) */
 int fk_gen_points_g1_dev(fk_ctx *ctx, void *d_out, size_t n, uint64_t seed);
@@ -404,7 +412,9 @@ int fk_prove_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r1cs, c
  * With a second ticket of the same key and system outstanding, _wait(k) also queues the FRONT of proof k+1 -- the evaluation of
  * a, b, c and the witness multiplications' sorts -- behind proof k's last accumulation, where proof k only has latency-bound
  * tails left (sizes that run the sorts-first schedule, 2^25 and up: "early front", csrc/spmv.hip); _wait(k+1) picks it up.
- * Between a _submit and its _wait only _submit / _wait may be called on the context. */
+ * While such a front is outstanding -- between _wait(k) and _wait(k+1) -- the context's staging buffers and lanes are proof k+1's: the
+ * entries marked [staging] below and in the other headers return FK_ERR_BAD_ARG ("... early front ... call fk_prove_r1cs_wait first")
+ * and drop nothing; the _dev hashing and signature entries keep running. */
 int fk_prove_r1cs_submit(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r1cs, const uint64_t *z,
                          const uint64_t r[4], const uint64_t s[4], int *ticket);
 int fk_prove_r1cs_wait(fk_ctx *ctx, int ticket, uint8_t out_proof[FK_PROOF_BYTES], fk_timings *timings);
@@ -580,6 +590,7 @@ int fk_multi_prove_r1cs_wait(fk_multi *multi, int ticket, uint8_t out_proof[FK_P
  * still returns FK_OK with the verdicts on the rest (fk_last_error then holds a note naming the first such proof). */
 int fk_verify(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uint64_t *inputs, uint32_t n_inputs,
               const uint8_t proof[FK_PROOF_BYTES], int *accept);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_verify_batch_dev(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uint64_t *inputs, uint32_t n_inputs,
                         const uint8_t *proofs, uint32_t count, uint8_t *accept);
 
@@ -602,22 +613,26 @@ int fk_poseidon_params_get(const fk_poseidon *params, uint32_t dims[3], uint64_t
 void fk_poseidon_free(fk_poseidon *params);
 /* poseidon(inputs, params) n times: hash i reads the n_inputs consecutive elements inputs[i * n_inputs ..], the rest of the state is
  * zero, out[i] = state[0] after the permutation.  0 < n_inputs < t, else FK_ERR_BAD_ARG; n == 0 is a no-op. */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_hash_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *inputs, uint32_t n_inputs, size_t n, uint64_t *out);
 int fk_poseidon_hash_batch_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_inputs, uint32_t n_inputs, size_t n, void *d_out);
 /* poseidon_sponge n times over messages of one length: message i is inputs[i * len ..]; the absorbed stream is Fr(len) followed by the
  * message, taken t - 1 elements at a time, each chunk ADDED into state[0 .. chunk) before a permutation.  len == 0 absorbs the length
  * word alone (inputs may then be NULL). */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_sponge_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *inputs, uint64_t len, size_t n, uint64_t *out);
 /* poseidon_merkle_tree_root with the whole tree kept.  L = ceil(log2 n_leaves); d_nodes holds 2^(L + 1) - 1 elements: level 0 = the
  * leaves, zero-padded to 2^L, then the higher levels in order, the root last (n_leaves == 1: L = 0, the root IS the leaf).  d_leaves
  * may be d_nodes itself.  t = 3 parameters only; t != 3 or n_leaves == 0 is FK_ERR_BAD_ARG.  _dev is asynchronous on the library's stream. */
 int fk_poseidon_merkle_tree_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_leaves, uint64_t n_leaves, void *d_nodes);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_merkle_root(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *leaves, uint64_t n_leaves, uint64_t *out_root);
 /* The `depth` siblings (leaf level first) of n leaves of a built tree of 2^depth leaves: d_siblings[i * depth + j], d_indices n x u64.
  * An index >= 2^depth is FK_ERR_BAD_ARG: it is found on the device, reads nothing and leaves zeros in its row.  Blocks until done. */
 int fk_poseidon_merkle_proofs_dev(fk_ctx *ctx, const void *d_nodes, uint32_t depth, const void *d_indices, size_t n, void *d_siblings);
 /* poseidon_merkle_proof_root n times: at level j bit j of indices[i] picks poseidon([sibling, root]) (set) or poseidon([root, sibling]);
  * bits from `depth` up are not looked at.  siblings: n x depth, proof-major.  depth <= 64; depth == 0 gives the leaf.  t = 3 only. */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_merkle_proof_roots(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *leaves, const uint64_t *siblings,
                                    const uint64_t *indices, uint32_t depth, size_t n, uint64_t *out);
 int fk_poseidon_merkle_proof_roots_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_leaves, const void *d_siblings,
@@ -643,11 +658,15 @@ int fk_poseidon_merkle_proof_roots_dev(fk_ctx *ctx, const fk_poseidon *params, c
  *                             is rejected (0) and the call still returns FK_OK: the reference's types cannot hold such values.
  *   fk_eddsa_verify_batch_dev the same on device arrays (d_s .. d_m n x 32 bytes, d_accept n bytes); asynchronous on the library's stream. */
 int fk_jubjub_params(uint64_t d[4], uint64_t g[8], uint64_t fs[4]);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_jubjub_mul_batch(fk_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t n, uint64_t *out);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_jubjub_decompress_batch(fk_ctx *ctx, const uint64_t *x, size_t n, uint64_t *y, uint8_t *ok);
 int fk_eddsa_hash_r(const uint64_t sk[4], const uint64_t m[4], uint64_t rho[4]);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_eddsa_sign_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *sk, const uint64_t *m, const uint64_t *rho, size_t n,
                         uint64_t *s, uint64_t *r_x, uint64_t *a_x);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_eddsa_verify_batch(fk_ctx *ctx, const fk_poseidon *params, const uint64_t *s, const uint64_t *r, const uint64_t *a, const uint64_t *m,
                           size_t n, uint8_t *accept);
 int fk_eddsa_verify_batch_dev(fk_ctx *ctx, const fk_poseidon *params, const void *d_s, const void *d_r, const void *d_a, const void *d_m,

@@ -41,6 +41,7 @@ int fk_r1cs_check(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, const uint64_
                   uint64_t *bad_bitmap, uint8_t *group_bad, fk_check_report *report);
 /* device: d_z as for fk_prove_r1cs_dev; d_bad_bitmap / d_group_bad are device pointers, either may be NULL; report is a host
  * pointer; blocks until it is filled. */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_r1cs_check_dev(fk_ctx *ctx, const fk_r1cs_dev *r1cs, const void *d_z, uint64_t group_rows,
                       void *d_bad_bitmap, void *d_group_bad, fk_check_report *report);
 /* fk_prove_r1cs_dev plus the check of the SAME evaluation: the check kernels run on the evaluated a, b, c between the

@@ -32,15 +32,18 @@ extern "C" {
 
 /* apply k leaf writes IN ORDER to a resident tree; any of the three outputs may be NULL.  Everything but the index check (one flag is
  * downloaded before the first write) is queued on the context's stream: fk_sync, or a download, before the outputs are read. */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_merkle_update_dev(fk_ctx *ctx, const fk_poseidon *params, void *d_nodes, uint32_t depth,
                                   const void *d_indices /* k x u64 */, const void *d_new_leaves /* k x Fr */, size_t k,
                                   void *d_old_leaves /* k x Fr */, void *d_siblings /* k x depth x Fr */, void *d_roots /* k x Fr */);
 /* the same with the writes and the outputs in host memory (Montgomery limbs, as everywhere); the tree stays resident; blocks */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_merkle_update(fk_ctx *ctx, const fk_poseidon *params, void *d_nodes, uint32_t depth,
                               const uint64_t *indices, const uint64_t *new_leaves, size_t k,
                               uint64_t *old_leaves, uint64_t *siblings, uint64_t *roots);
 /* measurement aid (tools/merkle_update_bench.py): fk_poseidon_merkle_update_dev, then a wait; ms[0] = the whole update on the device,
  * ms[1] = its `depth` hash launches alone (HIP events around each) */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_poseidon_merkle_update_timed_dev(fk_ctx *ctx, const fk_poseidon *params, void *d_nodes, uint32_t depth,
                                         const void *d_indices, const void *d_new_leaves, size_t k,
                                         void *d_old_leaves, void *d_siblings, void *d_roots, double ms[2]);

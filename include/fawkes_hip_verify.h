@@ -48,6 +48,7 @@ typedef struct {
  * milliseconds) on the host; all pointers are host pointers; it blocks until the verdict is known. */
 int fk_verify_aggregate(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uint64_t *inputs, uint32_t n_inputs, const uint8_t *proofs,
                         uint32_t count, const uint64_t *weights, uint8_t *wellformed, int *accept, fk_verify_agg_report *report);
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_verify_aggregate_dev(fk_ctx *ctx, const uint8_t *vk, size_t vk_len, const uint64_t *inputs, uint32_t n_inputs, const uint8_t *proofs,
                             uint32_t count, const uint64_t *weights, uint8_t *wellformed, int *accept, fk_verify_agg_report *report);
 

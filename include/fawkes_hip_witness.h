@@ -59,6 +59,7 @@ void fk_witness_program_free(fk_ctx *ctx, fk_witness_prog *prog);
  * batch does not fit 32-bit variable indices.  A witness that violates the circuit (a bad signature) is generated like any other. */
 int fk_witness_generate_dev(fk_ctx *ctx, const fk_witness_prog *prog, const void *d_given, uint32_t copies, void *d_z);
 /* the same with host buffers; blocks until z is written */
+/* [staging] refused while a submitted proof's early front is outstanding (fk_prove_r1cs_submit) */
 int fk_witness_generate(fk_ctx *ctx, const fk_witness_prog *prog, const uint64_t *given, uint32_t copies, uint64_t *z);
 
 #ifdef __cplusplus
