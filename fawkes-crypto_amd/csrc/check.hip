@@ -294,7 +294,7 @@ int fk_prove_r1cs_checked_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev 
         queued = true;
         return FK_OK;
     };
-    const int rc = prove_r1cs_dev_impl(ctx, key, r, d_z, rr, ss, out_proof, tm, &after_eval);
+    const int rc = prove_r1cs_dev_impl(ctx, key, r, d_z, rr, ss, out_proof, tm, &after_eval, nullptr);
     if (rc != FK_OK) {
         if (queued) (void)hipStreamSynchronize(ctx->stream);        // the caller's arrays are no longer written when an error returns
         return rc;

@@ -81,9 +81,24 @@ static constexpr int MSM_LANES = 4;   // B pair, L, A and H each on a lane of th
 // Which variables feed the A and the B query, as index lists (they are structural: a resident constraint system
 // computes them once at load).  With them the per-proof scalar compaction is one gather per query, no host round trip.
 struct QueryIdx {
-    const uint8_t *d_a_aux = nullptr, *d_b_in = nullptr, *d_b_aux = nullptr;   // the density maps the lists were made from
     const uint32_t *a = nullptr, *b = nullptr;                                 // variable indices, query order
     uint64_t n_a = 0, n_b = 0;
+};
+
+// ---- what ONE run of the prover is given besides key and vectors.  These are arguments, handed down the calls: nothing of them is kept in
+// the context, so an early return or an exception leaves nothing behind (what does survive a call is listed at proof_holds_lanes below).
+struct WitnessQueries {                 // which variables feed the A and the B query of this run
+    const uint8_t *d_a_aux = nullptr, *d_b_in = nullptr, *d_b_aux = nullptr;   // density maps: compacted per proof when idx is null
+    const QueryIdx *idx = nullptr;                                             // a resident system's index lists: one gather per query
+};
+struct FrontOpts {                      // how witness_begin queues the four witness multiplications
+    bool defer_back = false;            // sorts-first schedule: only the front of each now, the rest by msm_run_deferred (msm_begin)
+    bool gather_on_main = false;        // early front: the query gathers go on the main stream
+};
+struct ProveRun {
+    WitnessQueries q;
+    bool z_recorded = false;            // ctx->ev_z was recorded where z became complete: the prover does not record it again
+    const std::function<int()> *before_block = nullptr;      // called when everything of this proof is queued, before the prover blocks on the results
 };
 
 // Fixed-base precomputation of one key array (msm.hip): level w holds 2^(offset of window w) * P for every base P, so that
@@ -113,22 +128,16 @@ struct fk_ctx : fk::CtxScratch {
     // witness multiplications (L, A, B1, B2) in flight: begun before / while the quotient runs on the main stream
     hipStream_t aux = nullptr;          // scalar compaction for the A / B queries
     hipEvent_t ev_aux = nullptr, ev_main = nullptr, ev_z = nullptr;
-    // sorts-first schedule (prover.hip): with defer_back set, msm_begin queues only the front of a multiplication (digits, sort,
+    // sorts-first schedule (prover.hip): asked to defer, msm_begin queues only the front of a multiplication (digits, sort,
     // size ordering) and leaves the rest (accumulation, oversized buckets, reduction, download) here, to be queued by
     // msm_run_deferred once the caller has put the quotient between the two
-    bool defer_back = false;
     std::vector<std::function<int()>> deferred, deferred_tails;     // accumulations; tails
-    bool ev_z_recorded = false;
     hipEvent_t ev_acc_done = nullptr; bool ev_acc_done_valid = false;   // behind the most recent bucket accumulation (any lane)
     bool wit_active = false;
     // Early front (pipelined proofs, sorts-first schedule): while proof k's last kernels run -- latency-bound tails that leave the GPU
     // mostly idle -- the memory-bound front of proof k+1 (evaluation of a, b, c and the witness sorts) is already queued behind
-    // proof k's last accumulation.  before_block: called by the prover when everything of proof k is queued, before it blocks on
-    // the results; early: what that front left for proof k+1's run to pick up.
-    std::function<int()> before_block;
-    bool gather_on_main = false;
+    // proof k's last accumulation (ProveRun::before_block queues it).  early: what that front left for proof k+1's run to pick up.
     struct EarlyFront { bool done = false; int tails[4] = {-1, -1, -1, -1}; const fk_key *key = nullptr; const struct fk_r1cs_dev *r1cs = nullptr; const void *d_z = nullptr; } early;
-    const fk::QueryIdx *qidx = nullptr;   // set by the resident-constraint-system entry points for the duration of a call
     int wit_tail[4] = {-1, -1, -1, -1}; // B1, B2, L, A
     // witness hand-over from host memory (fk_witness_upload_async / fk_prove_r1cs_submit): two device slots filled on a copy
     // stream of their own, so that the upload of proof k+1's witness runs underneath proof k
@@ -208,10 +217,9 @@ namespace fk {
 // (spmv.hip: early_front) and fk_prove_r1cs_wait of that ticket picks them up.
 static inline bool proof_holds_staging(const fk_ctx *ctx) { return ctx->early.done; }
 // The MSM lanes: the above, or witness multiplications begun and not collected (fk_prove_msms_z_begin_dev .. _finish_dev) with whatever of
-// them is still deferred.  defer_back is set and cleared inside one call and deferred_tails is filled and drained together with deferred, so on
-// entry to a call the two add nothing to `deferred` -- unless an exception cut such a call short, and then refusing is right as well.
+// them is still deferred (deferred_tails is filled and drained together with deferred).
 static inline bool proof_holds_lanes(const fk_ctx *ctx) {
-    return proof_holds_staging(ctx) || ctx->wit_active || ctx->defer_back || !ctx->deferred.empty() || !ctx->deferred_tails.empty();
+    return proof_holds_staging(ctx) || ctx->wit_active || !ctx->deferred.empty() || !ctx->deferred_tails.empty();
 }
 
 // The claim every entry point that borrows the staging buffers or the lanes opens with, in place of its hipSetDevice line: selects the
@@ -400,9 +408,10 @@ int msm_g1_dev(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t
 // msm_abandon drops them all (error paths); msm_sync waits for both lanes.
 // ready: event after which bases / scalars are valid (nullptr: everything queued on ctx->stream so far)
 // pre: the bases' precomputed levels (nullptr / empty / made for another n: the ordinary W-bucket-set path)
-int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr);
+// defer: queue only the front (digits, sort, size ordering); msm_run_deferred queues the rest (fk_ctx::deferred)
+int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr, bool defer = false);
 int msm_g1_end(fk_ctx *ctx, int tail, G1Xyzz *out);
-int msm_g2_begin(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr);
+int msm_g2_begin(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr, bool defer = false);
 // fills key->pre_* for the slices the key holds (FK_MSM_PRECOMP=0 disables; skipped silently when HBM is short); key_pre_free undoes
 int key_precompute(fk_ctx *ctx, fk_key *key);
 int key_levels_headroom(fk_ctx *ctx, const fk_key *key, int64_t *bytes);
@@ -412,10 +421,17 @@ void msm_abandon(fk_ctx *ctx);
 int msm_run_deferred(fk_ctx *ctx, hipEvent_t after);
 int upload_deferred(fk_ctx *ctx, bool gate_on_main);      // queues the witness uploads fk_prove_r1cs_submit left for later
 int witness_slot_reserve(fk_ctx *ctx, int slot, size_t bytes, bool *moved = nullptr);      // prover.hip: room for `bytes` in a witness slot (+ its stream and events)
-int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const void *d_a_aux, const void *d_b_in, const void *d_b_aux, int tails_out[4]);   // prover.hip
+// prover.hip: the prover behind the extern "C" entries, with what a run is given as arguments (ProveRun)
+int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q, int tails_out[4]);
 bool early_front_applies(const fk_key *key);
+int witness_queries_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q);      // fk_prove_msms_z_begin_dev
+int witness_queries_finish(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_MSM_RESULT_BYTES]);      // fk_prove_msms_finish_dev
+int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, const Fr *d_z, const ProveRun &run,
+                   uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm);
+int prove_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, const Fr *d_z, const ProveRun &run, const uint64_t r[4],
+              const uint64_t s[4], uint8_t out[FK_PROOF_BYTES], fk_timings *tm);      // the multiplications, the assembly, the timings
 void msm_release(fk_ctx *ctx);
-int streams_init(fk_ctx *ctx);       // msm.hip: the context's copy / auxiliary / lane streams, created together in a fixed order (fk_init)
+int streams_init(fk_ctx *ctx);       // msm.hip: the context's copy / auxiliary / lane streams, created together in a fixed order, and its events (fk_init)
 int msm_sync(fk_ctx *ctx);
 // reuse_sort: the scalars are the ones of the immediately preceding MSM call on this context (same pointer
 // and n), so its digits / bucket sort are still valid and are not recomputed (B1 and B2 share scalars)

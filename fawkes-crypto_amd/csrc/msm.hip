@@ -8,7 +8,7 @@
 // MI355X pipeline (no MFMA -- 256-bit modular integer work).  A multiplication is queued on one of MSM_LANES lanes (stream +
 // private scratch); consecutive multiplications use different lanes, so the latency-bound steps 4-5 of one run underneath
 // steps 1-3 of the next (msm_*_begin / msm_*_end).  Its front (steps 1-2b), its accumulation (3) and its tail (4-5) can be
-// queued separately (fk_ctx::defer_back, msm_run_deferred): the prover's sorts-first schedule puts the quotient between the
+// queued separately (msm_begin's `defer`, msm_run_deferred): the prover's sorts-first schedule puts the quotient between the
 // witness multiplications' fronts and their accumulations (prover.hip).
 //   1. msm_digits      scalars leave Montgomery form (bellman's `into_repr`) and are cut into W signed digits; the 255
 //                      bits are split evenly into windows of cb or cb + 1 bits (no short top window).
@@ -997,6 +997,8 @@ int streams_init(fk_ctx *ctx) {
         FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_in, hipEventDisableTiming));
         FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_sorted, hipEventDisableTiming));
     }
+    // (events take no part in that mapping: the ones every proof records come with the streams, so that no caller creates one on demand)
+    for (hipEvent_t *e : {&ctx->ev_main, &ctx->ev_z, &ctx->ev_upload_gate}) if (!*e) FK_HIP(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
     return FK_OK;
 }
 
@@ -1010,7 +1012,7 @@ static int pinned_reserve(fk_ctx *ctx, void **p, size_t *cap, size_t bytes, size
 }
 
 // What the stages of one multiplication share: msm_begin fills it in, msm_reserve binds the pointers into the lane's scratch, the
-// deferred pieces (ctx->defer_back) keep a copy.
+// deferred pieces (msm_begin's `defer`) keep a copy.
 template <class F>
 struct MsmJob {
     fk_ctx *ctx;
@@ -1220,11 +1222,11 @@ static int queue_tail(MsmJob<F> j) {
 }
 
 // Lane `li` has been taken: the next multiplication goes to the lane after it.
-static void lanes_advance(fk_ctx *ctx, int li) {
+static void lanes_advance(fk_ctx *ctx, int li, bool defer = false) {
     // FK_MSM_LANES (experiment builds): fewer lanes -- never while pieces are deferred (sorts-first schedule): its deferred
     // accumulations and tails hold pointers into their lane's buffers, so every multiplication needs a lane of its own there
     static const int t_lanes = tune("FK_MSM_LANES", 0);
-    const int n_lanes = (t_lanes >= 1 && t_lanes <= MSM_LANES && !ctx->defer_back && ctx->deferred.empty())
+    const int n_lanes = (t_lanes >= 1 && t_lanes <= MSM_LANES && !defer && ctx->deferred.empty())
                             ? t_lanes : (ctx->lanes_in_use >= 2 && ctx->lanes_in_use <= MSM_LANES ? ctx->lanes_in_use : MSM_LANES);
     ctx->lane_prev = li; ctx->lane_next = (li + 1) % n_lanes;
 }
@@ -1235,7 +1237,7 @@ static void lanes_advance(fk_ctx *ctx, int li) {
 // the first proof of a size).  The five multiplications of a proof are therefore in the lanes' queues microseconds after
 // the quotient's kernels, and the GPU decides what runs underneath what.
 template <class F>
-static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail_out, hipEvent_t ready, const KeyPre *pre = nullptr) {
+static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail_out, hipEvent_t ready, const KeyPre *pre = nullptr, bool defer = false) {
     *tail_out = -1;
     if (n == 0) return FK_OK;
     if (n >= ((size_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: n too large");
@@ -1258,7 +1260,7 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
     const int li = have_sort ? ctx->lane_prev : ctx->lane_next;
     MsmLane &ln = ctx->lanes[li];
     if (!ln.st) FK_SET_ERR(ctx, FK_ERR_HIP, "msm: the context's streams were not created");      // (streams_init: fk_init, fk_trim)
-    lanes_advance(ctx, li);
+    lanes_advance(ctx, li, defer);
     if (ready) FK_HIP(ctx, hipStreamWaitEvent(ln.st, ready, 0));      // (the front of the multiplication runs on the lane's stream as well)
     else {
         FK_HIP(ctx, hipEventRecord(ln.ev_in, ctx->stream));        // scalars / bases produced on the main stream
@@ -1279,9 +1281,9 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
     tl.active = true; tl.cb = p.cb; tl.wide = p.wide; tl.W = job.WR; tl.nblk = 1;     // merged: one "window" of weight 1
     *tail_out = ti;
     // The back of the multiplication in two pieces -- the accumulation, and the tail (oversized buckets, reduction, download) --
-    // queued now, or by msm_run_deferred (ctx->defer_back): all accumulations first, then all tails, so that on the B pair's lane
+    // queued now, or by msm_run_deferred (`defer`): all accumulations first, then all tails, so that on the B pair's lane
     // the G2 accumulation follows the G1 one at once and both tails come behind (B2 has a bucket buffer of its own for that).
-    if (ctx->defer_back) {
+    if (defer) {
         ctx->deferred.push_back([job] { return queue_accumulate<F>(job); });
         ctx->deferred_tails.push_back([job] { return queue_tail<F>(job); });
         return FK_OK;
@@ -1336,7 +1338,7 @@ int msm_sync(fk_ctx *ctx) {
 void msm_abandon(fk_ctx *ctx) {
     ctx->wit_active = false;
     ctx->early.done = false;
-    ctx->defer_back = false; ctx->deferred.clear(); ctx->deferred_tails.clear();
+    ctx->deferred.clear(); ctx->deferred_tails.clear();
     if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
     for (int i = 0; i < MSM_TAILS; i++) ctx->tails[i].active = false;
     for (MsmLane &ln : ctx->lanes) { if (ln.st) (void)hipStreamSynchronize(ln.st); ln.last_sort_scalars = nullptr; }
@@ -1369,12 +1371,12 @@ void msm_release(fk_ctx *ctx) {
     }
 }
 
-int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready, const KeyPre *pre) {
-    return msm_begin<Fq>(ctx, d_bases, d_scalars, n, false, tail, ready, pre);
+int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready, const KeyPre *pre, bool defer) {
+    return msm_begin<Fq>(ctx, d_bases, d_scalars, n, false, tail, ready, pre, defer);
 }
 int msm_g1_end(fk_ctx *ctx, int tail, G1Xyzz *out) { return msm_end<Fq>(ctx, tail, out); }
-int msm_g2_begin(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail, hipEvent_t ready, const KeyPre *pre) {
-    return msm_begin<Fq2>(ctx, d_bases, d_scalars, n, reuse_sort, tail, ready, pre);
+int msm_g2_begin(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail, hipEvent_t ready, const KeyPre *pre, bool defer) {
+    return msm_begin<Fq2>(ctx, d_bases, d_scalars, n, reuse_sort, tail, ready, pre, defer);
 }
 int msm_g2_end(fk_ctx *ctx, int tail, G2Xyzz *out) { return msm_end<Fq2>(ctx, tail, out); }
 

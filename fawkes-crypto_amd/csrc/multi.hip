@@ -297,10 +297,8 @@ static int prove_rank(fk_multi *M, int rank, const fk_multi_key *K, const fk_mul
     FK_HIP(ctx, hipSetDevice(ctx->device));
     void *d_z = nullptr;
     FK_TRY(fk_witness_ptr(ctx, slot, &d_z));
-    if (rs->num_input != key->num_input || rs->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
-    const uint64_t rows = rs->num_gates + rs->num_input;
-    if (rows > key->m || (key->m > 1 && rows <= key->m / 2)) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: %llu rows do not match key domain %llu",
-                                                                     (unsigned long long)rows, (unsigned long long)key->m);
+    uint64_t rows = 0;
+    FK_TRY(r1cs_fits_key(ctx, rs, key, &rows));
     if (M->n == 1 && !M->force_exchange) return fk_prove_r1cs_dev(ctx, key, rs, d_z, r_, s_, out, tm);       // nothing to cut: the single-GPU prover
     const uint32_t log_m = ceil_log2_u64(key->m);
     uint8_t *part = me.part;
@@ -312,10 +310,7 @@ static int prove_rank(fk_multi *M, int rank, const fk_multi_key *K, const fk_mul
             const size_t mb = key->m * sizeof(Fr);
             FK_HIP(ctx, ctx->stage_a.reserve(mb)); FK_HIP(ctx, ctx->stage_b.reserve(mb)); FK_HIP(ctx, ctx->stage_c.reserve(mb));
             FK_TRY(fk_r1cs_eval_dev(ctx, rs, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p));
-            ctx->qidx = &rs->qidx;
-            const int rc = fk_prove_msms_dev(ctx, key, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, rows, d_z, rs->d_a_aux, rs->d_b_in, rs->d_b_aux, part, nullptr);
-            ctx->qidx = nullptr;
-            FK_TRY(rc);
+            FK_TRY(prove_msms_dev(ctx, key, ctx->stage_a.as<Fr>(), ctx->stage_b.as<Fr>(), ctx->stage_c.as<Fr>(), rows, (const Fr *)d_z, ProveRun{r1cs_queries(rs)}, part, nullptr));
         } else {
             FK_TRY(fk_prove_msms_hz_r1cs_dev(ctx, key, rs, nullptr, d_z, part));          // witness multiplications only: this rank holds no h
         }
@@ -344,10 +339,7 @@ static int prove_rank(fk_multi *M, int rank, const fk_multi_key *K, const fk_mul
         const size_t mb = key->m * sizeof(Fr);
         FK_HIP(ctx, ctx->stage_a.reserve(mb)); FK_HIP(ctx, ctx->stage_b.reserve(mb)); FK_HIP(ctx, ctx->stage_c.reserve(mb));
         FK_TRY(fk_r1cs_eval_dev(ctx, rs, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p));
-        ctx->qidx = &rs->qidx;
-        const int rc = fk_prove_msms_dev(ctx, key, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, rows, d_z, rs->d_a_aux, rs->d_b_in, rs->d_b_aux, part, nullptr);
-        ctx->qidx = nullptr;
-        FK_TRY(rc);
+        FK_TRY(prove_msms_dev(ctx, key, ctx->stage_a.as<Fr>(), ctx->stage_b.as<Fr>(), ctx->stage_c.as<Fr>(), rows, (const Fr *)d_z, ProveRun{r1cs_queries(rs)}, part, nullptr));
     }
     // "all-reduce of the partial sums": there is no elliptic-curve reduction operator to hand to a collective, so the N 384-byte
     // records meet in host memory (they are host results already: the window sums are folded on the host) and rank 0 folds them
@@ -777,7 +769,7 @@ static int multi_prove_slot(fk_multi *M, const fk_multi_key *K, const fk_multi_r
     const int rc = run_all(M, [&](int r) { return prove_rank(M, r, K, R, slot, r_, s_, out, tm, seq0); });
     if (rc != FK_OK) {
         // leave every rank in a state from which the next call can start: nothing queued, no multiplication outstanding
-        for (int r = 0; r < M->n; r++) { (void)hipSetDevice(M->dev[r]); msm_abandon(M->ctx[r]); M->ctx[r]->qidx = nullptr; (void)hipStreamSynchronize(M->ctx[r]->stream); (void)hipStreamSynchronize(M->ranks[r].xs); }
+        for (int r = 0; r < M->n; r++) { (void)hipSetDevice(M->dev[r]); msm_abandon(M->ctx[r]); (void)hipStreamSynchronize(M->ctx[r]->stream); (void)hipStreamSynchronize(M->ranks[r].xs); }
         for (auto &rk : M->ranks) rk.posted.store(M->seq);
         return rc;
     }

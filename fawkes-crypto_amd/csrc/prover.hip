@@ -293,8 +293,6 @@ int upload_deferred(fk_ctx *ctx, bool gate_on_main) {
         if (!w.deferred) continue;
         w.deferred = false;
         if (gate_on_main) {
-            if (!ctx->copy_st) FK_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_st, hipStreamNonBlocking));
-            if (!ctx->ev_upload_gate) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_upload_gate, hipEventDisableTiming));
             FK_HIP(ctx, hipEventRecord(ctx->ev_upload_gate, ctx->stream));
             FK_HIP(ctx, hipStreamWaitEvent(ctx->copy_st, ctx->ev_upload_gate, 0));
         }
@@ -499,41 +497,37 @@ static bool sorts_first(const fk_key *key) {
     return t >= 0 ? t != 0 : key->h_hi - key->h_lo >= (1ull << 25) - 1;       // by this context's share of H: a rank of a multi-GPU job holds 1/N
 }
 
-static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const uint8_t *d_a_aux, const uint8_t *d_b_in,
-                         const uint8_t *d_b_aux, hipEvent_t z_ready) {
+// Three lanes keep A from queueing behind B2's long G2 tail: 2^20 14.9 -> 13.3 ms, 2^22 28.0 -> 25.6 ms per proof.  At 2^25
+// it depends on the witness: with mostly trivial B-query scalars (the synthetic shape) the tails are short and a third
+// lane's co-running costs 1 %, with dense ones (1024 rollup transactions: G2 accumulation 35 ms) it gains 2 % -- 216.0 ->
+// 211.2 ms (profiles/r02_lanes_probe.log; one lane, no overlap at all: 227.3).  Since a multiplication is queued without
+// a host round trip (msm.hip) the picture at the top end changed: at 2^25 two lanes are 1 % ahead of three (195.1 vs
+// 197.5 ms, one lane 207.2), below that three still win by 1.5-5 % (profiles/r02_async_msm_ab_probe.log).
+// In the sorts-first schedule (prove_msms_dev) every multiplication has a lane of its own.
+static void lanes_choose(fk_ctx *ctx, const fk_key *key) { ctx->lanes_in_use = sorts_first(key) ? MSM_LANES : 3; }
+
+static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const WitnessQueries &q, hipEvent_t z_ready, FrontOpts opt = {}) {
     if (!key || !d_z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
     if (ctx->wit_active) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: witness multiplications already in flight");
     bool any_tail = false;
     for (int i = 0; i < MSM_TAILS; i++) any_tail = any_tail || ctx->tails[i].active;
     if (!any_tail) ctx->lane_next = 0;      // nothing outstanding: start the rotation over (same lanes in every proof)
-    // Three lanes keep A from queueing behind B2's long G2 tail: 2^20 14.9 -> 13.3 ms, 2^22 28.0 -> 25.6 ms per proof.  At 2^25
-    // it depends on the witness: with mostly trivial B-query scalars (the synthetic shape) the tails are short and a third
-    // lane's co-running costs 1 %, with dense ones (1024 rollup transactions: G2 accumulation 35 ms) it gains 2 % -- 216.0 ->
-    // 211.2 ms (profiles/r02_lanes_probe.log; one lane, no overlap at all: 227.3).  Since a multiplication is queued without
-    // a host round trip (msm.hip) the picture at the top end changed: at 2^25 two lanes are 1 % ahead of three (195.1 vs
-    // 197.5 ms, one lane 207.2), below that three still win by 1.5-5 % (profiles/r02_async_msm_ab_probe.log).
-    // In the sorts-first schedule (prove_msms_dev) every multiplication has a lane of its own.
-    ctx->lanes_in_use = sorts_first(key) ? MSM_LANES : 3;
+    lanes_choose(ctx, key);
     FK_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->aux) {
-        FK_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-        FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
-    }
     const uint32_t v_in = key->num_input, v_aux = key->num_aux;
     for (int i = 0; i < 4; i++) ctx->wit_tail[i] = -1;
     auto body = [&]() -> int {
         // the gathers of the A / B query scalars: on the auxiliary stream -- or, for an early front (the previous proof's tails are
         // still running and HIP maps more streams than there are hardware queues: the auxiliary stream was seen waiting behind the
         // G2 tail of the B pair's lane), on the main stream, which has nothing queued but the evaluation that follows
-        hipStream_t ax = ctx->gather_on_main ? ctx->stream : ctx->aux;
-        if (z_ready && !ctx->gather_on_main) FK_HIP(ctx, hipStreamWaitEvent(ax, z_ready, 0));
+        hipStream_t ax = opt.gather_on_main ? ctx->stream : ctx->aux;
+        if (z_ready && !opt.gather_on_main) FK_HIP(ctx, hipStreamWaitEvent(ax, z_ready, 0));
         // B query: inputs and aux variables that occur in some B-side LC;  A query: all inputs, then the aux variables
         // that occur in some A-side LC
         FK_HIP(ctx, ctx->sc_b.reserve(((size_t)v_in + v_aux) * sizeof(Fr)));
         FK_HIP(ctx, ctx->sc_a.reserve(((size_t)v_in + v_aux) * sizeof(Fr)));
         Fr *sb = ctx->sc_b.as<Fr>(), *sa = ctx->sc_a.as<Fr>();
-        const QueryIdx *qi = ctx->qidx;
-        if (qi && qi->d_a_aux == d_a_aux && qi->d_b_in == d_b_in && qi->d_b_aux == d_b_aux) {
+        if (const QueryIdx *qi = q.idx) {
             // resident constraint system: gather this key's slice of each query straight from the index lists
             if (qi->n_b != key->n_b) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: b query needs %llu points, key holds %llu",
                                                 (unsigned long long)qi->n_b, (unsigned long long)key->n_b);
@@ -552,22 +546,22 @@ static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const ui
             FK_TRY(gather_scalars(ctx, d_z, qi->a + key->a_lo, key->a_hi - key->a_lo, sa + key->a_lo, ax));
         } else {
             uint64_t n_b_in = 0, n_b_aux = 0, n_a_aux = 0;
-            FK_TRY(compact_scalars(ctx, d_z, d_b_in, v_in, sb, &n_b_in, ax));
-            FK_TRY(compact_scalars(ctx, d_z + v_in, d_b_aux, v_aux, sb + n_b_in, &n_b_aux, ax));
+            FK_TRY(compact_scalars(ctx, d_z, q.d_b_in, v_in, sb, &n_b_in, ax));
+            FK_TRY(compact_scalars(ctx, d_z + v_in, q.d_b_aux, v_aux, sb + n_b_in, &n_b_aux, ax));
             if (n_b_in + n_b_aux != key->n_b) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: b query needs %llu points, key holds %llu",
                                                          (unsigned long long)(n_b_in + n_b_aux), (unsigned long long)key->n_b);
             FK_HIP(ctx, hipMemcpyAsync(sa, d_z, (size_t)v_in * sizeof(Fr), hipMemcpyDeviceToDevice, ax));
-            FK_TRY(compact_scalars(ctx, d_z + v_in, d_a_aux, v_aux, sa + v_in, &n_a_aux, ax));
+            FK_TRY(compact_scalars(ctx, d_z + v_in, q.d_a_aux, v_aux, sa + v_in, &n_a_aux, ax));
             if (v_in + n_a_aux != key->n_a) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: a query needs %llu points, key holds %llu",
                                                        (unsigned long long)(v_in + n_a_aux), (unsigned long long)key->n_a);
         }
         FK_HIP(ctx, hipEventRecord(ctx->ev_aux, ax));
-        FK_TRY(msm_g1_begin(ctx, key->d_b1, sb + key->b_lo, key->b_hi - key->b_lo, &ctx->wit_tail[0], ctx->ev_aux, &key->pre_b1));
+        FK_TRY(msm_g1_begin(ctx, key->d_b1, sb + key->b_lo, key->b_hi - key->b_lo, &ctx->wit_tail[0], ctx->ev_aux, &key->pre_b1, opt.defer_back));
         // B2: the same scalars as B1 when the two slices coincide (B1's sort is reused); its own slice when the key is split by work
         FK_TRY(msm_g2_begin(ctx, key->d_b2, sb + key->b2_lo, key->b2_hi - key->b2_lo, /*reuse_sort=*/key->b2_lo == key->b_lo && key->b2_hi == key->b_hi,
-                            &ctx->wit_tail[1], ctx->ev_aux, &key->pre_b2));
-        FK_TRY(msm_g1_begin(ctx, key->d_l, d_z + v_in + key->l_lo, key->l_hi - key->l_lo, &ctx->wit_tail[2], z_ready ? z_ready : ctx->ev_aux, &key->pre_l));   // L reads z itself: it need not wait for the gathers
-        FK_TRY(msm_g1_begin(ctx, key->d_a, sa + key->a_lo, key->a_hi - key->a_lo, &ctx->wit_tail[3], ctx->ev_aux, &key->pre_a));
+                            &ctx->wit_tail[1], ctx->ev_aux, &key->pre_b2, opt.defer_back));
+        FK_TRY(msm_g1_begin(ctx, key->d_l, d_z + v_in + key->l_lo, key->l_hi - key->l_lo, &ctx->wit_tail[2], z_ready ? z_ready : ctx->ev_aux, &key->pre_l, opt.defer_back));   // L reads z itself: it need not wait for the gathers
+        FK_TRY(msm_g1_begin(ctx, key->d_a, sa + key->a_lo, key->a_hi - key->a_lo, &ctx->wit_tail[3], ctx->ev_aux, &key->pre_a, opt.defer_back));
         return FK_OK;
     };
     const int rc = body();
@@ -580,13 +574,9 @@ extern "C++" {
 namespace fk {
 // The witness half of an early front (spmv.hip: early_front): L, A, B1, B2 of the NEXT proof begun with their accumulations and
 // tails deferred, exactly as prove_msms_dev's sorts-first path would begin them.  Returns 0 when the schedule does not apply.
-int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const void *d_a_aux, const void *d_b_in, const void *d_b_aux, int tails_out[4]) {
+int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q, int tails_out[4]) {
     if (!early_front_applies(key)) return 0;
-    ctx->defer_back = true;
-    ctx->gather_on_main = true;
-    const int rc = witness_begin(ctx, key, (const Fr *)d_z, (const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux, ctx->ev_z);
-    ctx->gather_on_main = false;
-    ctx->defer_back = false;
+    const int rc = witness_begin(ctx, key, (const Fr *)d_z, q, ctx->ev_z, FrontOpts{/*defer_back=*/true, /*gather_on_main=*/true});
     if (rc != FK_OK) return -rc;
     memcpy(tails_out, ctx->wit_tail, 4 * sizeof(int));
     return 1;
@@ -622,22 +612,19 @@ static int witness_end(fk_ctx *ctx, uint8_t out[FK_MSM_RESULT_BYTES], int tail_h
     return FK_OK;
 }
 
-static int prove_msms_z(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const uint8_t *d_a_aux, const uint8_t *d_b_in,
-                        const uint8_t *d_b_aux, uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) {
+static int prove_msms_z(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const WitnessQueries &q, uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) {
     if (!out) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
     const double t0 = now_ms();
     FK_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_main) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
     FK_HIP(ctx, hipEventRecord(ctx->ev_main, ctx->stream));       // whatever produced z on the main stream
-    FK_TRY(witness_begin(ctx, key, d_z, d_a_aux, d_b_in, d_b_aux, ctx->ev_main));
+    FK_TRY(witness_begin(ctx, key, d_z, q, ctx->ev_main));
     FK_TRY(witness_end(ctx, out));
     if (tm) tm->msm_l_ms = now_ms() - t0;      // the four run interleaved; the sum is reported in the L slot
     return FK_OK;
 }
 
-static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, const Fr *d_z,
-                          const uint8_t *d_a_aux, const uint8_t *d_b_in, const uint8_t *d_b_aux, uint8_t out[FK_MSM_RESULT_BYTES],
-                          fk_timings *tm) {
+static int prove_msms_run(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, const Fr *d_z, const ProveRun &run,
+                          uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) {
     if (!key || !d_a || !d_b || !d_c || !d_z || !out) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
     if (n == 0 || n > key->m || (key->m > 1 && n <= key->m / 2)) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: %llu rows do not match key domain %llu",
                                                       (unsigned long long)n, (unsigned long long)key->m);
@@ -652,7 +639,7 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
     if (ctx->early.done && !early) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: an early front of another proof is outstanding"); }
     ctx->early.done = false;
     if (!early) ctx->lane_next = 0;     // same lane for the same multiplication in every proof: lane buffers keep their sizes
-    ctx->lanes_in_use = sorts_first(key) ? MSM_LANES : 3;      // measured, see witness_begin
+    lanes_choose(ctx, key);
     // The witness multiplications depend on z only: they are begun right behind the QUEUED quotient, so that their sorts (and what
     // fits of their accumulations) fill the transforms' gaps: 214.5 -> 206.9 ms per proof on the 1024-transaction system
     // (profiles/r02_cusplit_witness_first_probe.log), and at every smaller size measured -- synthetic 2^20 13.4 -> 11.1 ms,
@@ -660,12 +647,9 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
     // measured an earlier form of this overlap as a loss below 2^24.)  FK_PROVE_WITNESS_FIRST=0 puts the quotient first again.
     static const int t_wfirst = tune("FK_PROVE_WITNESS_FIRST", 1);
     const bool wfirst = t_wfirst != 0;
-    if (!ctx->ev_main) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
-    if (!ctx->ev_z) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_z, hipEventDisableTiming));
     // z is complete here -- or, for a resident constraint system, it already was before a, b, c were evaluated from it
     // (fk_prove_r1cs_dev): the witness multiplications then start together with that evaluation instead of behind it
-    if (!ctx->ev_z_recorded) FK_HIP(ctx, hipEventRecord(ctx->ev_z, ctx->stream));
-    ctx->ev_z_recorded = false;
+    if (!run.z_recorded) FK_HIP(ctx, hipEventRecord(ctx->ev_z, ctx->stream));
     // Sorts first (the kernel timeline of a proof, tools/trace_gantt.py, is what this follows): a sort's workgroups (1024
     // lanes, > 100 KB of LDS) make no headway underneath the transforms (two 64 KB workgroups per compute unit) nor underneath
     // an accumulation (the whole register file) -- a 1.5 ms scatter pass took 30 ms there and the accumulations behind it
@@ -683,9 +667,7 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
             memcpy(ctx->wit_tail, ctx->early.tails, sizeof ctx->wit_tail);      // begun by early_front (deferred pieces included)
             ctx->wit_active = true;
         } else {
-            ctx->defer_back = t_accgate != 0;
-            const int rcw = witness_begin(ctx, key, d_z, d_a_aux, d_b_in, d_b_aux, ctx->ev_z);
-            ctx->defer_back = false;
+            const int rcw = witness_begin(ctx, key, d_z, run.q, ctx->ev_z, FrontOpts{/*defer_back=*/t_accgate != 0});
             if (rcw != FK_OK) { msm_abandon(ctx); return rcw; }
         }
         for (MsmLane &ln : ctx->lanes)
@@ -707,7 +689,7 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
         // (H's sort right behind the quotient, ALONE, with every accumulation behind it was measured too: slower by 3-10 ms.)
         if (gate) { const int rcd = msm_run_deferred(ctx, ctx->ev_main); if (rcd != FK_OK) { msm_abandon(ctx); return rcd; } }
         if (!gate) {
-            const int rcw = witness_begin(ctx, key, d_z, d_a_aux, d_b_in, d_b_aux, ctx->ev_z);
+            const int rcw = witness_begin(ctx, key, d_z, run.q, ctx->ev_z);
             if (rcw != FK_OK) { msm_abandon(ctx); return rcw; }
         }
         int t_h0 = -1;
@@ -717,14 +699,12 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
         // Everything of this proof is queued.  Before blocking on its results: the front of the NEXT proof, if the caller has one
         // waiting (fk_prove_r1cs_wait) -- its witness multiplications become the context's current ones, so this proof's are
         // collected by their handles.
-        if (gate && ctx->before_block) {
+        if (gate && run.before_block) {
             int mine[4];
             memcpy(mine, ctx->wit_tail, sizeof mine);
             ctx->wit_active = false;
-            std::function<int()> hook;
-            hook.swap(ctx->before_block);
             int rce;
-            { FK_RANGE("prove: queue the NEXT proof's early front"); rce = hook(); }
+            { FK_RANGE("prove: queue the NEXT proof's early front"); rce = (*run.before_block)(); }
             if (rce != FK_OK) { msm_abandon(ctx); return rce; }
             { FK_RANGE("prove: wait for the five multiplications"); FK_TRY(witness_end(ctx, out, t_h0, mine)); }
         } else { FK_RANGE("prove: wait for the five multiplications"); FK_TRY(witness_end(ctx, out, t_h0)); }
@@ -735,13 +715,12 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
     // measured (2^20 .. 2^25): both sides are VALU-bound, nothing is gained at 2^25 and 10 % is lost at 2^20 / 2^22.  So was
     // running only their SORTS underneath it, accumulations held back until it is done: 2^25 139.5 -> 148.1 ms, 2^22 29.2 -> 34.0
     // (the B pair's sort alone: 138.6 -> 152.0 ms) -- an NTT pass moves 2.2 TB/s and holds 64 KB of LDS per workgroup, which the sort's workgroups compete for.
-    if (!ctx->ev_main) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
     FK_HIP(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
     // H first: it is the longest accumulation and hides the sorts of the multiplications behind it (B1, B2, H, L, A -- H after
     // the B pair, so that only B1's smaller sort is exposed -- measured 3 % slower at 2^25 and 13 % slower at 2^22)
     int t_h = -1;
     FK_TRY(msm_g1_begin(ctx, key->d_h, d_h + key->h_lo, key->h_hi - key->h_lo, &t_h, ctx->ev_main, &key->pre_h));
-    const int rc = witness_begin(ctx, key, d_z, d_a_aux, d_b_in, d_b_aux, ctx->ev_main);
+    const int rc = witness_begin(ctx, key, d_z, run.q, ctx->ev_main);
     if (rc != FK_OK) { msm_abandon(ctx); return rc; }
     const double t2 = now_ms();
     FK_TRY(witness_end(ctx, out, t_h));
@@ -749,11 +728,49 @@ static int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
     return FK_OK;
 }
 
+extern "C++" {
+namespace fk {
+// The prover as the library calls it, behind the entries below, spmv.hip's and multi.hip's.  Guarded here as well: an exception inside a run
+// reaches every caller as a status code, so what a caller does on an error (the checked proof synchronises, a rank of an fk_multi abandons) happens.
+int prove_msms_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, const Fr *d_z, const ProveRun &run,
+                   uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) {
+    return fk_guard(ctx, [&]() -> int { return prove_msms_run(ctx, key, d_a, d_b, d_c, n, d_z, run, out, tm); });
+}
+
+int prove_dev(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, const Fr *d_z, const ProveRun &run, const uint64_t r[4],
+              const uint64_t s[4], uint8_t out[FK_PROOF_BYTES], fk_timings *tm) {
+    if (key && key->shard_count != 1) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "fk_prove needs an unsharded key (use fk_prove_msms + fk_prove_assemble)");
+    if (tm) memset(tm, 0, sizeof *tm);
+    uint8_t msms[FK_MSM_RESULT_BYTES];
+    FK_TRY(prove_msms_dev(ctx, key, d_a, d_b, d_c, n, d_z, run, msms, tm));
+    const double t0 = now_ms();
+    FK_TRY(fk_prove_assemble(ctx, key, msms, 1, r, s, out));
+    if (tm) { tm->assemble_ms = now_ms() - t0; tm->total_ms += tm->assemble_ms; }
+    return FK_OK;
+}
+
+int witness_queries_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q) {
+    FK_HIP(ctx, hipSetDevice(ctx->device));
+    FK_HIP(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
+    return witness_begin(ctx, key, (const Fr *)d_z, q, ctx->ev_main);
+}
+
+int witness_queries_finish(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_MSM_RESULT_BYTES]) {
+    if (!key || !out || (!d_h_slice && key->h_hi > key->h_lo)) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument"); }
+    FK_HIP(ctx, hipSetDevice(ctx->device));
+    int t_h = -1;
+    const int rc = msm_g1_begin(ctx, key->d_h, (const Fr *)d_h_slice, key->h_hi - key->h_lo, &t_h, nullptr, &key->pre_h);
+    if (rc != FK_OK) { msm_abandon(ctx); return rc; }
+    return witness_end(ctx, out, t_h);
+}
+}  // namespace fk
+}  // extern "C++"
+
 int fk_prove_msms_z_dev(fk_ctx *ctx, const fk_key *key, const void *d_z, const void *d_a_aux, const void *d_b_in,
                         const void *d_b_aux, uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (tm) memset(tm, 0, sizeof *tm);
-    return prove_msms_z(ctx, key, (const Fr *)d_z, (const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux, out, tm);
+    return prove_msms_z(ctx, key, (const Fr *)d_z, {(const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux}, out, tm);
 }); }
 
 int fk_prove_msm_h_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_G1_BYTES]) { return fk_guard(ctx, [&]() -> int {
@@ -789,36 +806,28 @@ int fk_prove_msm_array_dev(fk_ctx *ctx, const fk_key *key, int which, const void
 
 int fk_prove_msms_z_begin_dev(fk_ctx *ctx, const fk_key *key, const void *d_z, const void *d_a_aux, const void *d_b_in, const void *d_b_aux) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
-    FK_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->ev_main) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
-    FK_HIP(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
-    return witness_begin(ctx, key, (const Fr *)d_z, (const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux, ctx->ev_main);
+    return witness_queries_begin(ctx, key, d_z, {(const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux});
 }); }
 
 int fk_prove_msms_finish_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_MSM_RESULT_BYTES]) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
-    if (!key || !out || (!d_h_slice && key->h_hi > key->h_lo)) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument"); }
-    FK_HIP(ctx, hipSetDevice(ctx->device));
-    int t_h = -1;
-    const int rc = msm_g1_begin(ctx, key->d_h, (const Fr *)d_h_slice, key->h_hi - key->h_lo, &t_h, nullptr, &key->pre_h);
-    if (rc != FK_OK) { msm_abandon(ctx); return rc; }
-    return witness_end(ctx, out, t_h);
+    return witness_queries_finish(ctx, key, d_h_slice, out);
 }); }
 
 int fk_prove_msms_hz_dev(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, const void *d_z, const void *d_a_aux, const void *d_b_in,
                          const void *d_b_aux, uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (tm) memset(tm, 0, sizeof *tm);
-    FK_TRY(fk_prove_msms_z_begin_dev(ctx, key, d_z, d_a_aux, d_b_in, d_b_aux));
-    return fk_prove_msms_finish_dev(ctx, key, d_h_slice, out);
+    FK_TRY(witness_queries_begin(ctx, key, d_z, {(const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux}));
+    return witness_queries_finish(ctx, key, d_h_slice, out);
 }); }
 
 int fk_prove_msms_dev(fk_ctx *ctx, const fk_key *key, void *d_a, void *d_b, void *d_c, uint64_t n, const void *d_z,
                       const void *d_a_aux, const void *d_b_in, const void *d_b_aux, uint8_t out[FK_MSM_RESULT_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (tm) memset(tm, 0, sizeof *tm);
-    return prove_msms_dev(ctx, key, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c, n, (const Fr *)d_z, (const uint8_t *)d_a_aux,
-                          (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux, out, tm);
+    return prove_msms_dev(ctx, key, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c, n, (const Fr *)d_z,
+                          ProveRun{{(const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux}}, out, tm);
 }); }
 
 // A = alpha + A_q + r*delta1 ; B = beta2 + B2 + s*delta2 ;
@@ -861,13 +870,8 @@ int fk_prove_dev(fk_ctx *ctx, const fk_key *key, void *d_a, void *d_b, void *d_c
                  const void *d_a_aux, const void *d_b_in, const void *d_b_aux, const uint64_t r[4], const uint64_t s[4],
                  uint8_t out[FK_PROOF_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
-    if (key && key->shard_count != 1) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "fk_prove needs an unsharded key (use fk_prove_msms + fk_prove_assemble)");
-    uint8_t msms[FK_MSM_RESULT_BYTES];
-    FK_TRY(fk_prove_msms_dev(ctx, key, d_a, d_b, d_c, n, d_z, d_a_aux, d_b_in, d_b_aux, msms, tm));
-    const double t0 = now_ms();
-    FK_TRY(fk_prove_assemble(ctx, key, msms, 1, r, s, out));
-    if (tm) { tm->assemble_ms = now_ms() - t0; tm->total_ms += tm->assemble_ms; }
-    return FK_OK;
+    return prove_dev(ctx, key, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c, n, (const Fr *)d_z,
+                     ProveRun{{(const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux}}, r, s, out, tm);
 }); }
 
 static int stage_inputs(fk_ctx *ctx, const fk_key *key, const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n,

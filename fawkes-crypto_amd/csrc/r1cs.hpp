@@ -76,8 +76,20 @@ struct fk_r1cs_dev {
 };
 
 namespace fk {
+// A resident system's queries as a run of the prover takes them (common.hpp: ProveRun): its index lists, no per-proof compaction.
+static inline WitnessQueries r1cs_queries(const fk_r1cs_dev *r) { return {r->d_a_aux, r->d_b_in, r->d_b_aux, &r->qidx}; }
+// The one check that a system belongs to a key.  rows (may be null: only the witness multiplications follow, no transform): the rows
+// a, b, c get -- the gates and one row per input -- which must fill more than half of the key's domain and no more than all of it.
+static inline int r1cs_fits_key(fk_ctx *ctx, const fk_r1cs_dev *r, const fk_key *key, uint64_t *rows) {
+    if (r->num_input != key->num_input || r->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
+    if (!rows) return FK_OK;
+    *rows = r->num_gates + r->num_input;
+    if (*rows > key->m || (key->m > 1 && *rows <= key->m / 2)) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: %llu rows do not match key domain %llu",
+                                                                       (unsigned long long)*rows, (unsigned long long)key->m);
+    return FK_OK;
+}
 // spmv.hip
 int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a, void *d_b, void *d_c, bool sliced, uint32_t rank, uint32_t log_w, uint64_t n_out, int window);
 int prove_r1cs_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
-                        uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval);
+                        uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval, const std::function<int()> *before_block);
 }  // namespace fk

@@ -646,7 +646,6 @@ static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1
         }
         if ((ia.size() && hipMemcpy(r->d_idx_a, ia.data(), ia.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
             (ib.size() && hipMemcpy(r->d_idx_b, ib.data(), ib.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
-        r->qidx.d_a_aux = r->d_a_aux; r->qidx.d_b_in = r->d_b_in; r->qidx.d_b_aux = r->d_b_aux;
         r->qidx.a = r->d_idx_a; r->qidx.b = r->d_idx_b; r->qidx.n_a = ia.size(); r->qidx.n_b = ib.size();
     }
     *out = r;
@@ -885,48 +884,37 @@ int fk_r1cs_eval_slice_dev(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, u
 
 }  // extern "C"
 namespace fk {
-// The body of fk_prove_r1cs_dev, shared with fk_prove_r1cs_checked_dev (check.hip).  after_eval (may be null): called once the evaluation
-// of a, b, c into the stage buffers is queued on the main stream and before the quotient that consumes them is; what it queues there
-// reads the very a, b, c the proof is made from.  An entry that passes one does not join the submit / wait pipeline: any outstanding
-// early front is refused.  With a null after_eval nothing differs from the body as it stood: same calls, same order.
+// The body of fk_prove_r1cs_dev, shared with fk_prove_r1cs_checked_dev (check.hip) and fk_prove_r1cs_wait.  after_eval (may be null): called
+// once the evaluation of a, b, c into the stage buffers is queued on the main stream and before the quotient that consumes them is; what it
+// queues there reads the very a, b, c the proof is made from.  An entry that passes one does not join the submit / wait pipeline: any
+// outstanding early front is refused.  before_block (may be null): ProveRun's.
 int prove_r1cs_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
-                        uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval) {
+                        uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval, const std::function<int()> *before_block) {
     if (!key || !r || !d_z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
-    if (r->num_input != key->num_input || r->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
-    const uint64_t rows = r->num_gates + r->num_input;
-    if (rows > key->m || (key->m > 1 && rows <= key->m / 2)) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: %llu rows do not match key domain %llu",
-                                                                     (unsigned long long)rows, (unsigned long long)key->m);
+    uint64_t rows = 0;
+    FK_TRY(r1cs_fits_key(ctx, r, key, &rows));
     FK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t mb = key->m * sizeof(Fr);
     if (after_eval && ctx->early.done) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: an early front of a submitted proof is outstanding"); }
+    ProveRun run{r1cs_queries(r), false, before_block};      // the queries' index lists are known: no per-proof density compaction
     if (ctx->early.done && ctx->early.key == key && ctx->early.r1cs == r && ctx->early.d_z == d_z) {
         // the front of this proof -- ev_z, the evaluation of a, b, c into the stage buffers, the witness multiplications' sorts --
         // was queued while the previous proof's tails ran (early_front below): go on with the quotient
-        ctx->qidx = &r->qidx;
-        ctx->ev_z_recorded = true;
-        const int rc = fk_prove_dev(ctx, key, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, rows, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux, rr, ss, out_proof, tm);
-        ctx->qidx = nullptr;
-        ctx->ev_z_recorded = false;
-        return rc;
+        run.z_recorded = true;
+    } else {
+        if (ctx->early.done) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: an early front of another proof is outstanding"); }
+        FK_HIP(ctx, ctx->stage_a.reserve(mb)); FK_HIP(ctx, ctx->stage_b.reserve(mb)); FK_HIP(ctx, ctx->stage_c.reserve(mb));
+        // z is complete at this point of the main stream: the witness multiplications wait for THIS, not for the evaluation of a, b, c
+        // (11.6 ms at 2^25 during which nothing else ran; FK_PROVE_Z_EARLY=0 restores that)
+        static const int t_zearly = tune("FK_PROVE_Z_EARLY", 1);
+        if (t_zearly) {
+            FK_HIP(ctx, hipEventRecord(ctx->ev_z, ctx->stream));
+            run.z_recorded = true;
+        }
+        FK_TRY(fk_r1cs_eval_dev(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p));
+        if (after_eval) FK_TRY((*after_eval)());
     }
-    if (ctx->early.done) { msm_abandon(ctx); FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: an early front of another proof is outstanding"); }
-    FK_HIP(ctx, ctx->stage_a.reserve(mb)); FK_HIP(ctx, ctx->stage_b.reserve(mb)); FK_HIP(ctx, ctx->stage_c.reserve(mb));
-    // z is complete at this point of the main stream: the witness multiplications wait for THIS, not for the evaluation of a, b, c
-    // (11.6 ms at 2^25 during which nothing else ran; FK_PROVE_Z_EARLY=0 restores that)
-    static const int t_zearly = tune("FK_PROVE_Z_EARLY", 1);
-    if (t_zearly) {
-        if (!ctx->ev_z) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_z, hipEventDisableTiming));
-        FK_HIP(ctx, hipEventRecord(ctx->ev_z, ctx->stream));
-        ctx->ev_z_recorded = true;
-    }
-    ctx->qidx = &r->qidx;      // the queries' index lists are known: no per-proof density compaction
-    int rce = fk_r1cs_eval_dev(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p);
-    if (rce == FK_OK && after_eval) rce = (*after_eval)();
-    if (rce != FK_OK) { ctx->qidx = nullptr; ctx->ev_z_recorded = false; return rce; }
-    const int rc = fk_prove_dev(ctx, key, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, rows, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux, rr, ss, out_proof, tm);
-    ctx->qidx = nullptr;
-    ctx->ev_z_recorded = false;
-    return rc;
+    return prove_dev(ctx, key, ctx->stage_a.as<Fr>(), ctx->stage_b.as<Fr>(), ctx->stage_c.as<Fr>(), rows, (const Fr *)d_z, run, rr, ss, out_proof, tm);
 }
 }  // namespace fk
 extern "C" {
@@ -936,7 +924,7 @@ int fk_prove_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, cons
                       uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm) { return fk_guard(ctx, [&]() -> int {
     FK_RANGE("fk_prove_r1cs_dev");
     if (!ctx) return FK_ERR_BAD_ARG;
-    return prove_r1cs_dev_impl(ctx, key, r, d_z, rr, ss, out_proof, tm, nullptr);
+    return prove_r1cs_dev_impl(ctx, key, r, d_z, rr, ss, out_proof, tm, nullptr, nullptr);
 }); }
 
 // multi-GPU: all five multiplications of this key's slices for a resident constraint system (see fk_prove_msms_hz_dev)
@@ -944,11 +932,9 @@ int fk_prove_msms_hz_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev 
                               uint8_t out[FK_MSM_RESULT_BYTES]) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!key || !r || !d_z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
-    if (r->num_input != key->num_input || r->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
-    ctx->qidx = &r->qidx;
-    const int rc = fk_prove_msms_hz_dev(ctx, key, d_h_slice, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux, out, nullptr);
-    ctx->qidx = nullptr;
-    return rc;
+    FK_TRY(r1cs_fits_key(ctx, r, key, nullptr));
+    FK_TRY(witness_queries_begin(ctx, key, d_z, r1cs_queries(r)));
+    return witness_queries_finish(ctx, key, d_h_slice, out);
 }); }
 
 // ... and of fk_prove_msms_z_begin_dev: the witness multiplications are queued (index-list gathers), the caller runs the
@@ -956,11 +942,8 @@ int fk_prove_msms_hz_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev 
 int fk_prove_msms_z_begin_r1cs_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z) { return fk_guard(ctx, [&]() -> int {
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!key || !r || !d_z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "prove: null argument");
-    if (r->num_input != key->num_input || r->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
-    ctx->qidx = &r->qidx;
-    const int rc = fk_prove_msms_z_begin_dev(ctx, key, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux);
-    ctx->qidx = nullptr;
-    return rc;
+    FK_TRY(r1cs_fits_key(ctx, r, key, nullptr));
+    return witness_queries_begin(ctx, key, d_z, r1cs_queries(r));
 }); }
 
 }  // extern "C"
@@ -972,20 +955,16 @@ namespace fk {
 // the last byte has landed instead of ~20 ms, and the witness sorts then run without the evaluation beside them.  A system whose first rows
 // read late variables degenerates to "upload everything, then evaluate" (win_need[0] = all of z).  Same kernels, same row order inside a
 // window, same bytes.
-static int prove_r1cs_chunked(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const uint64_t *z, const uint64_t rr[4], const uint64_t ss[4],
+static int prove_r1cs_chunked(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, uint64_t rows, const uint64_t *z, const uint64_t rr[4], const uint64_t ss[4],
                               uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm) {
-    const uint64_t rows = r->num_gates + r->num_input;
     const size_t mb = key->m * sizeof(Fr);
     FK_HIP(ctx, ctx->stage_a.reserve(mb)); FK_HIP(ctx, ctx->stage_b.reserve(mb)); FK_HIP(ctx, ctx->stage_c.reserve(mb));
-    if (!ctx->copy_st) FK_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_st, hipStreamNonBlocking));
-    if (!ctx->ev_upload_gate) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_upload_gate, hipEventDisableTiming));
-    if (!ctx->ev_z) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_z, hipEventDisableTiming));
     // the pieces follow whatever the main stream still has queued (stage_z may be read by it)
     FK_HIP(ctx, hipEventRecord(ctx->ev_upload_gate, ctx->stream));
     FK_HIP(ctx, hipStreamWaitEvent(ctx->copy_st, ctx->ev_upload_gate, 0));
     Fr *d_z = ctx->stage_z.as<Fr>();
     uint64_t off = 0;
-    ctx->qidx = &r->qidx;
+    ProveRun run{r1cs_queries(r)};
     int rc = FK_OK;
     // piece j, then window j: from pageable memory hipMemcpyAsync returns only when the piece has been staged, so the windows must be
     // queued BETWEEN the pieces for the evaluation to run beside the rest of the upload
@@ -999,15 +978,13 @@ static int prove_r1cs_chunked(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev 
         off = std::max(off, end);
         if (e == hipSuccess && j + 1 == r->win_k) {        // z is complete at this point of the main stream: the witness multiplications wait for THIS, not for the last window
             e = hipEventRecord(ctx->ev_z, ctx->stream);
-            ctx->ev_z_recorded = e == hipSuccess;
+            run.z_recorded = e == hipSuccess;
         }
         if (e != hipSuccess) { rc = FK_ERR_HIP; ctx->err = std::string("prove: chunked hand-over: ") + hipGetErrorString(e); break; }
         rc = r1cs_eval_impl(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, false, 0, 0, 0, (int)j);
     }
-    if (rc == FK_OK) rc = fk_prove_dev(ctx, key, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p, rows, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux, rr, ss, out_proof, tm);
-    else { (void)hipStreamSynchronize(ctx->copy_st); (void)hipStreamSynchronize(ctx->stream); }        // the caller's buffer is no longer read when an error returns
-    ctx->qidx = nullptr;
-    ctx->ev_z_recorded = false;
+    if (rc == FK_OK) return prove_dev(ctx, key, ctx->stage_a.as<Fr>(), ctx->stage_b.as<Fr>(), ctx->stage_c.as<Fr>(), rows, d_z, run, rr, ss, out_proof, tm);
+    (void)hipStreamSynchronize(ctx->copy_st); (void)hipStreamSynchronize(ctx->stream);        // the caller's buffer is no longer read when an error returns
     return rc;
 }
 }  // namespace fk
@@ -1023,11 +1000,9 @@ int fk_prove_r1cs(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const ui
     FK_HIP(ctx, ctx->stage_z.reserve(zb));
     static const bool t_chunked = !(getenv("FK_PROVE_CHUNKED_UPLOAD") && atoi(getenv("FK_PROVE_CHUNKED_UPLOAD")) == 0);      // documented switch (fawkes_hip.h)
     if (t_chunked && r->win_k >= 2 && !ctx->early.done && !ctx->wslot[0].pending && !ctx->wslot[1].pending) {
-        if (r->num_input != key->num_input || r->num_aux != key->num_aux) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: constraint system and key disagree on the variable counts");
-        const uint64_t rows = r->num_gates + r->num_input;
-        if (rows > key->m || (key->m > 1 && rows <= key->m / 2)) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: %llu rows do not match key domain %llu",
-                                                                         (unsigned long long)rows, (unsigned long long)key->m);
-        return prove_r1cs_chunked(ctx, key, r, z, rr, ss, out_proof, tm);
+        uint64_t rows = 0;
+        FK_TRY(r1cs_fits_key(ctx, r, key, &rows));
+        return prove_r1cs_chunked(ctx, key, r, rows, z, rr, ss, out_proof, tm);
     }
     FK_HIP(ctx, hipMemcpyAsync(ctx->stage_z.p, z, zb, hipMemcpyHostToDevice, ctx->stream));
     return fk_prove_r1cs_dev(ctx, key, r, ctx->stage_z.p, rr, ss, out_proof, tm);
@@ -1073,16 +1048,12 @@ static int early_front(fk_ctx *ctx, int slot) {
     if (ctx->ev_acc_done_valid) FK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_acc_done, 0));      // ... and for the current proof's last accumulation (H's)
     const size_t mb = key->m * sizeof(Fr);
     if (mb > ctx->stage_a.cap || mb > ctx->stage_b.cap || mb > ctx->stage_c.cap) return FK_OK;       // never grow buffers the current proof may still read: no early front
-    if (!ctx->ev_z) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_z, hipEventDisableTiming));
     FK_HIP(ctx, hipEventRecord(ctx->ev_z, ctx->stream));
-    ctx->qidx = &r->qidx;
     int tails[4];
-    const int wb = early_witness_begin(ctx, key, d_z, r->d_a_aux, r->d_b_in, r->d_b_aux, tails);
-    if (wb < 0) { ctx->qidx = nullptr; return -wb; }
-    if (wb == 0) { ctx->qidx = nullptr; return FK_OK; }     // (the schedule does not apply: nothing was queued but the waits)
-    const int rce = fk_r1cs_eval_dev(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p);
-    ctx->qidx = nullptr;
-    if (rce != FK_OK) return rce;
+    const int wb = early_witness_begin(ctx, key, d_z, r1cs_queries(r), tails);
+    if (wb < 0) return -wb;
+    if (wb == 0) return FK_OK;     // (the schedule does not apply: nothing was queued but the waits)
+    FK_TRY(fk_r1cs_eval_dev(ctx, r, d_z, ctx->stage_a.p, ctx->stage_b.p, ctx->stage_c.p));
     ctx->early.done = true; ctx->early.key = key; ctx->early.r1cs = r; ctx->early.d_z = d_z;
     memcpy(ctx->early.tails, tails, sizeof tails);
     return FK_OK;
@@ -1102,14 +1073,9 @@ int fk_prove_r1cs_wait(fk_ctx *ctx, int ticket, uint8_t out_proof[FK_PROOF_BYTES
     else FK_TRY(fk_witness_ptr(ctx, ticket, &d_z));
     // the other slot holds the NEXT proof of the same key and system: its front goes behind this proof's last accumulation
     const fk_ctx::WitSlot &o = ctx->wslot[ticket ^ 1];
-    ctx->before_block = nullptr;
-    if (o.pending && o.key == w.key && o.r1cs == w.r1cs && early_front_applies(w.key)) {
-        const int other = ticket ^ 1;
-        ctx->before_block = [ctx, other]() { return early_front(ctx, other); };
-    }
-    const int rc = fk_prove_r1cs_dev(ctx, w.key, w.r1cs, d_z, w.r, w.s, out_proof, tm);
-    ctx->before_block = nullptr;
-    return rc;
+    const std::function<int()> front = [ctx, ticket]() { return early_front(ctx, ticket ^ 1); };
+    const bool next = o.pending && o.key == w.key && o.r1cs == w.r1cs && early_front_applies(w.key);
+    return prove_r1cs_dev_impl(ctx, w.key, w.r1cs, d_z, w.r, w.s, out_proof, tm, nullptr, next ? &front : nullptr);
 }); }
 
 }  // extern "C"

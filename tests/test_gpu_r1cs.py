@@ -264,3 +264,19 @@ def test_prove_chunked_hand_over_same_bytes(ctx, local):
         ctx.dev_free(d_z)
         dr.free()
         key.free()
+
+
+@pytest.mark.parametrize('sorts_first', ['1', '0'])
+def test_prove_chunked_hand_over_under_either_schedule(sorts_first):
+    """The chunked hand-over records ev_z itself and tells the prover so; under the sorts-first schedule (on by default only from 2^25 on,
+    read once per process -> subprocess) the witness multiplications are begun against that event before the quotient.  The child proves
+    two witnesses of a 70001-gate system with row windows chunked, whole and through submit / wait: same bytes (tests/_chunked_child.py)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith(('FK_MSM_', 'FK_PROVE_', 'FK_SPMV_', 'FK_NTT_'))}
+    env['FK_PROVE_SORTS_FIRST'] = sorts_first
+    out = subprocess.run([sys.executable, os.path.join(root, 'tests', '_chunked_child.py')], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert len([l for l in out.stdout.splitlines() if l.startswith('CHUNKED ok')]) == 1, out.stdout[-1000:]
