@@ -22,3 +22,5 @@ from . import witness  # noqa: F401
 from . import verify_agg  # noqa: F401
 from . import check  # noqa: F401
 from . import merkle  # noqa: F401
+from . import sparse_merkle  # noqa: F401
+from .sparse_merkle import SparseMerkleTree  # noqa: F401

@@ -22,34 +22,12 @@
 // level 0, or the stored leaf.
 //
 // Scratch per call (documented in the header): cur / next (2 k Fr, ctx->stage_a); keys, next keys (k u64 each), order, next order,
-// previous touchers (k u32 each) (ctx->stage_b); the sort's temporary storage (ctx->stage_c).  This is the library's one use of rocPRIM.
-#include "poseidon.hpp"
+// previous touchers (k u32 each) (ctx->stage_b); the sort's temporary storage (ctx->stage_c).  This sort and the same one in sparse_merkle.hip are the library's use of rocPRIM.
+#include "merkle_plan.hpp"      // the index check, the plan kernel and the drivers' small helpers: shared with sparse_merkle.hip
 #include "../../include/fawkes_hip_merkle.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace fk {
-
-static constexpr uint32_t MU_NONE = 0xffffffffu;
-
-__global__ __launch_bounds__(POS_THREADS) void mu_check_kernel(const uint64_t *__restrict__ idx, uint32_t k, uint32_t depth, uint32_t *bad) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < k && (idx[j] >> depth)) atomicOr(bad, 1u);
-}
-
-__global__ __launch_bounds__(POS_THREADS) void mu_iota_kernel(uint32_t *__restrict__ out, uint32_t k) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < k) out[j] = j;
-}
-
-// the first position in [lo, hi) whose element is not below x
-template <class T>
-static __device__ __forceinline__ uint32_t mu_lower_bound(const T *__restrict__ a, uint32_t lo, uint32_t hi, T x) {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // level 0 only: what each write replaces.  keys / ord: the level-0 order
 __global__ __launch_bounds__(POS_THREADS) void mu_old_leaves_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ord, uint32_t k,
@@ -58,26 +36,6 @@ __global__ __launch_bounds__(POS_THREADS) void mu_old_leaves_kernel(const uint64
     if (q >= k) return;
     const uint64_t node = keys[q];
     old[ord[q]] = (q > 0 && keys[q - 1] == node) ? new_leaves[ord[q - 1]] : leaves[node];
-}
-
-// keys[q] = index >> l of the write at position q, ord[q] = its j; sorted by (key, j)
-__global__ __launch_bounds__(POS_THREADS) void mu_plan_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ord, uint32_t k,
-                                                               uint32_t *__restrict__ prev, uint64_t *__restrict__ next_keys, uint32_t *__restrict__ next_ord) {
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= k) return;
-    const uint64_t node = keys[q], left = node & ~(uint64_t)1;
-    const uint32_t j = ord[q];
-    // [lo, mid) = the writes through the left child of the parent, [mid, hi) = those through the right one; lo <= q < hi
-    const uint32_t lo = mu_lower_bound(keys, 0u, q, left);
-    const uint32_t mid = mu_lower_bound(keys, lo, k, left | 1);
-    const uint32_t hi = mu_lower_bound(keys, mid > q ? mid : q, k, left + 2);
-    const bool right = node & 1;
-    const uint32_t a = right ? mid : lo, c = right ? lo : mid, d = right ? mid : hi;
-    const uint32_t r = mu_lower_bound(ord, c, d, j) - c;
-    prev[j] = r ? ord[c + r - 1] : MU_NONE;
-    const uint32_t pos = lo + (q - a) + r;
-    next_ord[pos] = j;
-    next_keys[pos] = node >> 1;
 }
 
 // level: the stored nodes of level l; cur: the writes' values at level l (by j); sib_out: siblings + l, or null
@@ -106,15 +64,6 @@ __global__ __launch_bounds__(POS_THREADS) void mu_write_back_kernel(const uint64
     const uint64_t node = keys[q];
     if (q + 1 == k || keys[q + 1] != node) level[node] = cur[ord[q]];
 }
-
-struct MuEvents {       // HIP events of one timed call
-    std::vector<hipEvent_t> ev;
-    ~MuEvents() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t make(size_t n) {
-        for (size_t i = 0; i < n; i++) { hipEvent_t e; const hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; ev.push_back(e); }
-        return hipSuccess;
-    }
-};
 
 static int update_args(fk_ctx *ctx, const fk_poseidon *h, uint32_t depth, size_t k) {
     if (!h) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
@@ -194,11 +143,6 @@ static int update_dev(fk_ctx *ctx, const fk_poseidon *h, Fr *d_nodes, uint32_t d
     }
     return FK_OK;
 }
-
-struct MuDevBlock {     // device copies of the host entry's arguments: freed on every path
-    void *p = nullptr;
-    ~MuDevBlock() { if (p) (void)hipFree(p); }
-};
 
 }  // namespace fk
 

@@ -8,7 +8,8 @@ returns what each transaction's circuit needs: the leaf it replaced, its sibling
 whatever the collisions among the indices.
 
 The C prototypes of these entry points live in this module's own table (the table of _abi.py mirrors fawkes_hip.h and nothing else).
-Limits: one GPU; the tree resident and dense (2^(depth + 1) - 1 nodes); at most 2^28 writes per call.
+Limits: one GPU; the tree resident and dense (2^(depth + 1) - 1 nodes: for a tree too deep for that, sparse_merkle.SparseMerkleTree
+offers the same update over the stored nodes alone); at most 2^28 writes per call.
 """
 import ctypes as C
 
