@@ -24,3 +24,4 @@ from . import check  # noqa: F401
 from . import merkle  # noqa: F401
 from . import sparse_merkle  # noqa: F401
 from .sparse_merkle import SparseMerkleTree  # noqa: F401
+from . import merkle_set  # noqa: F401

@@ -1,9 +1,30 @@
-// Shared by merkle_update.hip (dense trees) and sparse_merkle.hip (sparse trees): the part of an ordered update that depends on the
-// leaf indices alone -- the index check, the identity order the stable sort starts from, and the per-level plan (previous toucher of
-// every write's sibling, and the next level's order, merkle_update.hip's header comment) -- with the small host helpers of both drivers.
+// Shared by merkle_update.hip (dense trees) and sparse_merkle.hip (sparse trees).
+//
+// The ordered update: the part that depends on the leaf indices alone -- the index check, the identity order the stable sort starts
+// from, and the per-level plan (previous toucher of every write's sibling, and the next level's order, merkle_update.hip's header
+// comment) -- with the small host helpers of both drivers.
+//
+// The bulk write ("set", include/fawkes_hip_merkle_set.h): everything but how a level is stored.  The same check and the same stable
+// sort; then the LAST element of every run of equal indices is selected into an ascending list of m_0 distinct (key, value) pairs, and
+// per level l = 0 .. depth - 1:
+//   write-back  one list element per lane: the level's store takes (key, value).  The keys are distinct
+//   select      the heads of the runs of equal key >> 1 are the m_(l + 1) distinct parents: rocPRIM's select over the positions
+//               0 .. bound - 1 writes the heads' positions, compacted, and their number -- to device memory, where the next launches
+//               read it.  The host launches with its bound min(k, 2^(depth - l)); lanes at or past the device's count leave
+//   hash        one PARENT per lane, lanes dense: lane i < m_(l + 1) takes head i.  Its other child is the head's neighbour in the
+//               list, or is not in the list and is read from the level's store (the default where the store has none)
+// so a node is hashed once however many writes pass through it.  A node of level l is either in the list (written) or read as an
+// absent child, never both, and the write-back is a launch of its own in FRONT of the hash launch of its level: the hash launch reads
+// a store that no lane is writing, and nothing has to be argued about a probe beside a claim.
+// A store is a small struct passed by value: put(key, value), and get(key) -> where the value of a node that is not in the list lies.
+//
 // The kernels have internal linkage: each of the two translation units carries its own copy in its own code object.
 #pragma once
 #include "poseidon.hpp"
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <algorithm>
 
 namespace fk {
 
@@ -62,5 +83,170 @@ struct MuDevBlock {     // device copies of a host entry's arguments: freed on e
     void *p = nullptr;
     ~MuDevBlock() { if (p) (void)hipFree(p); }
 };
+
+// ------------------------------------------------------------------------------------------ the bulk write
+// rocPRIM's select asks these of a position (a uint32_t from a counting iterator)
+struct MsRunLast {          // keys: all k writes, sorted by (index, position)
+    const uint64_t *keys; uint32_t k;
+    __host__ __device__ bool operator()(uint32_t q) const { return q >= k - 1 || keys[q + 1] != keys[q]; }       // k >= 1
+};
+struct MsParentHead {       // keys: the *m distinct nodes of a level, ascending
+    const uint64_t *keys; const size_t *m;
+    __host__ __device__ bool operator()(uint32_t i) const { return i < *m && (i == 0 || (keys[i - 1] >> 1) != (keys[i] >> 1)); }
+};
+
+// level 0: src[i] = the position, in the sorted writes, of the last write to the i-th distinct index
+static __global__ __launch_bounds__(POS_THREADS) void ms_gather_kernel(const uint64_t *__restrict__ skeys, const uint32_t *__restrict__ ord, const Fr *__restrict__ leaves,
+                                                                        const uint32_t *__restrict__ src, const size_t *__restrict__ m, uint32_t bound,
+                                                                        uint64_t *__restrict__ keys, Fr *__restrict__ vals) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= bound || i >= *m) return;
+    const uint32_t q = src[i];
+    keys[i] = skeys[q];
+    vals[i] = leaves[ord[q]];
+}
+
+template <class Store>
+static __global__ __launch_bounds__(POS_THREADS) void ms_write_back_kernel(const uint64_t *__restrict__ keys, const Fr *__restrict__ vals, const size_t *__restrict__ m,
+                                                                            uint32_t bound, Store st) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= bound || i >= *m) return;
+    st.put(keys[i], vals[i]);
+}
+
+// keys / vals: the m[0] nodes of the level; src: the positions of the m[1] heads; st: the level's store
+template <class Store>
+static __global__ __launch_bounds__(POS_THREADS) void ms_hash_kernel(const Fr *__restrict__ tab, uint32_t f, uint32_t p, const uint64_t *__restrict__ keys,
+                                                                      const Fr *__restrict__ vals, const uint32_t *__restrict__ src, const size_t *__restrict__ m,
+                                                                      uint32_t bound, Store st, uint64_t *__restrict__ next_keys, Fr *__restrict__ next_vals) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= bound || i >= m[1]) return;
+    const uint32_t at = src[i];
+    const uint64_t node = keys[at];
+    // the head is the left child with the right one behind it, or the parent's only child in the list
+    const bool pair = !(node & 1) && at + 1 < m[0] && keys[at + 1] == (node | 1);
+    const Fr *from = pair ? vals + at + 1 : st.get(node ^ 1);
+    const Fr sib = *from;
+    const Fr own = vals[at];
+    const bool right = node & 1;
+    Fr x, y;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { x.v[j] = right ? sib.v[j] : own.v[j]; y.v[j] = right ? own.v[j] : sib.v[j]; }
+    next_keys[i] = node >> 1;
+    next_vals[i] = hash2(tab, f, p, x, y);
+}
+
+static inline uint64_t ms_level_bound(uint32_t depth, uint32_t l, uint32_t k) { return std::min<uint64_t>(k, (uint64_t)1 << (depth - l)); }      // depth - l <= 63
+
+struct MsTimed { double *ms; uint64_t *distinct; };     // what a timed entry wants back (either may be null): then the call waits for the stream
+
+// the staging of one call, carved after every buffer has its size: list values | sorted keys, list keys, the counts m_0 .. m_depth,
+// order, identity, positions | rocPRIM's temporary storage.  92 bytes per write and 8 * (depth + 1), the temporary storage apart
+struct MsScratch {
+    Fr *val[2]; uint64_t *key[2]; size_t *counts; uint32_t *ord, *iota, *src; void *tmp; size_t sort_bytes, select_bytes;
+};
+
+static int ms_reserve(fk_ctx *ctx, const uint64_t *d_idx, uint32_t depth, uint32_t k, MsScratch *s) {
+    s->sort_bytes = s->select_bytes = 0;
+    FK_HIP(ctx, rocprim::radix_sort_pairs(nullptr, s->sort_bytes, d_idx, (uint64_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)k, 0u, depth, ctx->stream));
+    FK_HIP(ctx, rocprim::select(nullptr, s->select_bytes, rocprim::counting_iterator<uint32_t>(0), (uint32_t *)nullptr, (size_t *)nullptr, (size_t)k,
+                                MsParentHead{nullptr, nullptr}, ctx->stream));
+    size_t run_last = 0;
+    FK_HIP(ctx, rocprim::select(nullptr, run_last, rocprim::counting_iterator<uint32_t>(0), (uint32_t *)nullptr, (size_t *)nullptr, (size_t)k, MsRunLast{nullptr, 0}, ctx->stream));
+    s->select_bytes = std::max(s->select_bytes, run_last);
+    FK_HIP(ctx, ctx->stage_a.reserve((size_t)2 * k * sizeof(Fr)));
+    FK_HIP(ctx, ctx->stage_b.reserve((size_t)k * (2 * sizeof(uint64_t) + 3 * sizeof(uint32_t)) + (size_t)(depth + 1) * sizeof(size_t)));
+    FK_HIP(ctx, ctx->stage_c.reserve(std::max<size_t>(std::max(s->sort_bytes, s->select_bytes), 8)));
+    s->val[0] = ctx->stage_a.as<Fr>(); s->val[1] = s->val[0] + k;
+    s->key[1] = ctx->stage_b.as<uint64_t>(); s->key[0] = s->key[1] + k;        // the sorted writes' keys lie where the list of level 1 goes
+    s->counts = (size_t *)(s->key[0] + k);
+    s->ord = (uint32_t *)(s->counts + depth + 1); s->iota = s->ord + k; s->src = s->iota + k;
+    s->tmp = ctx->stage_c.p;
+    return FK_OK;
+}
+
+// the index check of both trees: one flag comes to the host, and nothing has been written when it does
+static int ms_check_indices(fk_ctx *ctx, uint32_t *flag, const uint64_t *d_idx, uint32_t k, uint32_t depth, const char *tree) {
+    FK_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(mu_check_kernel, dim3(pos_blocks(k)), dim3(POS_THREADS), 0, ctx->stream, d_idx, k, depth, flag);
+    FK_HIP(ctx, hipGetLastError());
+    uint32_t bad = 0;
+    FK_HIP(ctx, hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: a leaf index of the set is not below 2^%u (nothing was written: the tree and the root output are as they were)", tree, depth);
+    return FK_OK;
+}
+
+// depth 0: the tree is its root, the one leaf, and the last write wins.  k >= 1
+static int ms_set_depth0(fk_ctx *ctx, const Fr *d_leaves, uint32_t k, Fr *root, Fr *d_root_out, const MsTimed *timed) {
+    FK_HIP(ctx, hipMemcpyAsync(root, d_leaves + (k - 1), sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_root_out) FK_HIP(ctx, hipMemcpyAsync(d_root_out, d_leaves + (k - 1), sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    if (timed) {
+        FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (timed->ms) timed->ms[0] = timed->ms[1] = 0;
+        if (timed->distinct) timed->distinct[0] = 1;
+    }
+    return FK_OK;
+}
+
+// depth >= 1, k >= 1, the indices checked, `s` reserved (and, for a sparse tree, its capacity settled).  store_at(l): the store of
+// level l.  tm: null, or the events of a timed call: [0], [1] around everything, [2 + 2 l], [3 + 2 l] around the hash launch of level l
+template <class StoreAt>
+static int ms_set_levels(fk_ctx *ctx, const Fr *tab, uint32_t f, uint32_t p, uint32_t depth, const uint64_t *d_idx, const Fr *d_leaves, uint32_t k, const MsScratch &s,
+                         StoreAt store_at, Fr *root, Fr *d_root_out, MuEvents *tm) {
+    const dim3 block(POS_THREADS);
+    const rocprim::counting_iterator<uint32_t> positions(0);
+    size_t bytes = s.sort_bytes;
+    if (tm) FK_HIP(ctx, hipEventRecord(tm->ev[0], ctx->stream));
+    hipLaunchKernelGGL(mu_iota_kernel, dim3(pos_blocks(k)), block, 0, ctx->stream, s.iota, k);
+    FK_HIP(ctx, hipGetLastError());
+    uint64_t *skeys = s.key[1];
+    FK_HIP(ctx, rocprim::radix_sort_pairs(s.tmp, bytes, d_idx, skeys, (const uint32_t *)s.iota, s.ord, (size_t)k, 0u, depth, ctx->stream));
+    bytes = s.select_bytes;
+    FK_HIP(ctx, rocprim::select(s.tmp, bytes, positions, s.src, s.counts, (size_t)k, MsRunLast{skeys, k}, ctx->stream));
+    hipLaunchKernelGGL(ms_gather_kernel, dim3(pos_blocks(k)), block, 0, ctx->stream, (const uint64_t *)skeys, (const uint32_t *)s.ord, d_leaves, (const uint32_t *)s.src,
+                       (const size_t *)s.counts, k, s.key[0], s.val[0]);
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG(ctx, "merkle set: sort");
+    for (uint32_t l = 0; l < depth; l++) {
+        const uint32_t here = (uint32_t)ms_level_bound(depth, l, k), above = (uint32_t)ms_level_bound(depth, l + 1, k);
+        const uint64_t *keys = s.key[l & 1];
+        const Fr *vals = s.val[l & 1];
+        const size_t *m = s.counts + l;
+        const auto st = store_at(l);
+        hipLaunchKernelGGL(ms_write_back_kernel, dim3(pos_blocks(here)), block, 0, ctx->stream, keys, vals, m, here, st);
+        FK_HIP(ctx, hipGetLastError());
+        bytes = s.select_bytes;
+        FK_HIP(ctx, rocprim::select(s.tmp, bytes, positions, s.src, s.counts + l + 1, (size_t)here, MsParentHead{keys, m}, ctx->stream));
+        if (tm) FK_HIP(ctx, hipEventRecord(tm->ev[2 + 2 * l], ctx->stream));
+        hipLaunchKernelGGL(ms_hash_kernel, dim3(pos_blocks(above)), block, 0, ctx->stream, tab, f, p, keys, vals, (const uint32_t *)s.src, m, above, st, s.key[(l + 1) & 1],
+                           s.val[(l + 1) & 1]);
+        if (tm) FK_HIP(ctx, hipEventRecord(tm->ev[3 + 2 * l], ctx->stream));
+        FK_HIP(ctx, hipGetLastError());
+        FK_DBG(ctx, "merkle set: level");
+    }
+    // the list of level `depth` is the root alone
+    const Fr *top = s.val[depth & 1];
+    FK_HIP(ctx, hipMemcpyAsync(root, top, sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_root_out) FK_HIP(ctx, hipMemcpyAsync(d_root_out, top, sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    if (tm) FK_HIP(ctx, hipEventRecord(tm->ev[1], ctx->stream));
+    return FK_OK;
+}
+
+// the end of a timed call: the wait, the two times, the counts
+static int ms_finish_timed(fk_ctx *ctx, const MuEvents &tm, uint32_t depth, const MsScratch &s, const MsTimed &timed) {
+    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (timed.ms) {
+        float t = 0;
+        FK_HIP(ctx, hipEventElapsedTime(&t, tm.ev[0], tm.ev[1]));
+        timed.ms[0] = t; timed.ms[1] = 0;
+        for (uint32_t l = 0; l < depth; l++) { FK_HIP(ctx, hipEventElapsedTime(&t, tm.ev[2 + 2 * l], tm.ev[3 + 2 * l])); timed.ms[1] += t; }
+    }
+    if (timed.distinct) {
+        static_assert(sizeof(size_t) == sizeof(uint64_t), "the counts are downloaded as they lie");
+        FK_HIP(ctx, hipMemcpy(timed.distinct, s.counts, (size_t)(depth + 1) * sizeof(size_t), hipMemcpyDeviceToHost));
+    }
+    return FK_OK;
+}
 
 }  // namespace fk

@@ -22,9 +22,16 @@
 // level 0, or the stored leaf.
 //
 // Scratch per call (documented in the header): cur / next (2 k Fr, ctx->stage_a); keys, next keys (k u64 each), order, next order,
-// previous touchers (k u32 each) (ctx->stage_b); the sort's temporary storage (ctx->stage_c).  This sort and the same one in sparse_merkle.hip are the library's use of rocPRIM.
-#include "merkle_plan.hpp"      // the index check, the plan kernel and the drivers' small helpers: shared with sparse_merkle.hip
+// previous touchers (k u32 each) (ctx->stage_b); the sort's temporary storage (ctx->stage_c).  This sort, the same one in sparse_merkle.hip and the bulk write's
+// select (merkle_plan.hpp) are the library's use of rocPRIM.
+//
+// Set of k writes (include/fawkes_hip_merkle_set.h: the final tree of the update and nothing else): merkle_plan.hpp's bulk write with
+// the node array as the store of a level -- put is a plain store, get the address of the node.  The write-back of a level is a launch
+// of its own in front of the level's hash launch (the shared driver's order): a node is either written or read as an absent child,
+// never both, so the hash launch reads nodes that no launch beside it writes.
+#include "merkle_plan.hpp"      // the index check, the plan kernel, the bulk write and the drivers' small helpers: shared with sparse_merkle.hip
 #include "../../include/fawkes_hip_merkle.h"
+#include "../../include/fawkes_hip_merkle_set.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace fk {
@@ -144,6 +151,28 @@ static int update_dev(fk_ctx *ctx, const fk_poseidon *h, Fr *d_nodes, uint32_t d
     return FK_OK;
 }
 
+// a level as merkle_plan.hpp's bulk write sees it
+struct DenseStore {
+    Fr *level;
+    __device__ __forceinline__ void put(uint64_t key, const Fr &v) const { level[key] = v; }
+    __device__ __forceinline__ const Fr *get(uint64_t key) const { return level + key; }
+};
+
+// k >= 1, arguments checked, the staging claimed.  timed: null, or what the timed entry wants (then the call waits for the stream)
+static int set_dev(fk_ctx *ctx, const fk_poseidon *h, Fr *d_nodes, uint32_t depth, const uint64_t *d_idx, const Fr *d_leaves, uint32_t k, const MsTimed *timed) {
+    PosDev d; FK_TRY(pos_upload(ctx, h, &d));
+    FK_TRY(ms_check_indices(ctx, d.flag, d_idx, k, depth, "merkle"));
+    if (depth == 0) return ms_set_depth0(ctx, d_leaves, k, d_nodes, nullptr, timed);
+    MsScratch s; FK_TRY(ms_reserve(ctx, d_idx, depth, k, &s));
+    MuEvents tm;
+    if (timed) FK_HIP(ctx, tm.make(2 + 2 * (size_t)depth));
+    // level l begins behind the 2^depth + .. + 2^(depth - l + 1) nodes of the levels below it; the root is the last node
+    auto store_at = [&](uint32_t l) { return DenseStore{d_nodes + (((uint64_t)2 << depth) - ((uint64_t)2 << (depth - l)))}; };
+    FK_TRY(ms_set_levels(ctx, d.tab, h->f, h->p, depth, d_idx, d_leaves, k, s, store_at, d_nodes + (((uint64_t)2 << depth) - 2), (Fr *)nullptr, timed ? &tm : nullptr));
+    if (timed) FK_TRY(ms_finish_timed(ctx, tm, depth, s, *timed));
+    return FK_OK;
+}
+
 }  // namespace fk
 
 using namespace fk;
@@ -192,6 +221,49 @@ int fk_poseidon_merkle_update(fk_ctx *ctx, const fk_poseidon *h, void *d_nodes, 
         };
         rc = down();
     }
+    (void)hipStreamSynchronize(ctx->stream);      // the block is in use until the stream has drained, on the error paths too
+    return rc;
+}); }
+
+// ---- include/fawkes_hip_merkle_set.h
+int fk_poseidon_merkle_set_timed_dev(fk_ctx *ctx, const fk_poseidon *h, void *d_nodes, uint32_t depth, const void *d_indices, const void *d_leaves, size_t k,
+                                     double ms[2], uint64_t *distinct) { return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    FK_TRY(update_args(ctx, h, depth, k));
+    if (ms) ms[0] = ms[1] = 0;
+    if (!k) return FK_OK;
+    if (!d_nodes || !d_indices || !d_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_TRY(scratch_claim(ctx, "merkle set"));      // merkle_plan.hpp's bulk write sorts and selects in stage_a/b/c
+    const MsTimed timed{ms, distinct};
+    return set_dev(ctx, h, (Fr *)d_nodes, depth, (const uint64_t *)d_indices, (const Fr *)d_leaves, (uint32_t)k, &timed);
+}); }
+
+int fk_poseidon_merkle_set_dev(fk_ctx *ctx, const fk_poseidon *h, void *d_nodes, uint32_t depth, const void *d_indices, const void *d_leaves, size_t k) {
+    return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    FK_TRY(update_args(ctx, h, depth, k));
+    if (!k) return FK_OK;
+    if (!d_nodes || !d_indices || !d_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_TRY(scratch_claim(ctx, "merkle set"));
+    return set_dev(ctx, h, (Fr *)d_nodes, depth, (const uint64_t *)d_indices, (const Fr *)d_leaves, (uint32_t)k, nullptr);
+}); }
+
+int fk_poseidon_merkle_set(fk_ctx *ctx, const fk_poseidon *h, void *d_nodes, uint32_t depth, const uint64_t *indices, const uint64_t *leaves, size_t k) {
+    return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    FK_TRY(update_args(ctx, h, depth, k));
+    if (!k) return FK_OK;
+    if (!d_nodes || !indices || !leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_TRY(scratch_claim(ctx, "merkle set"));
+    // one block: leaves | indices
+    const size_t ib = k * sizeof(uint64_t), lb = k * sizeof(Fr);
+    MuDevBlock blk;
+    FK_HIP(ctx, hipMalloc(&blk.p, lb + ib));
+    Fr *d_leaves = (Fr *)blk.p;
+    uint64_t *d_idx = (uint64_t *)(d_leaves + k);
+    FK_HIP(ctx, hipMemcpyAsync(d_idx, indices, ib, hipMemcpyHostToDevice, ctx->stream));
+    FK_HIP(ctx, hipMemcpyAsync(d_leaves, leaves, lb, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = set_dev(ctx, h, (Fr *)d_nodes, depth, d_idx, d_leaves, (uint32_t)k, nullptr);
     (void)hipStreamSynchronize(ctx->stream);      // the block is in use until the stream has drained, on the error paths too
     return rc;
 }); }

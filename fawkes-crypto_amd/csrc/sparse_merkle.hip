@@ -24,8 +24,18 @@
 // by ONE small download queued at the end of each update into pinned memory behind an event; the next call takes them when they have
 // arrived and waits for them only if its upper bounds would otherwise force a growth.  Nothing is downloaded between levels.
 // Every probe loop is bounded by the capacity; one that runs out (by construction none does) sets the error word and stops its lane.
+//
+// Set of k writes (include/fawkes_hip_merkle_set.h: the final state of the update, the new root and nothing else): merkle_plan.hpp's
+// bulk write with this file's store of a level -- put claims the key's slot as the update's write-back does and stores the value
+// plainly (the keys of a launch are distinct), get is a bounded probe that falls back to zero[l].  The write-back of a level stays a
+// launch of its own, in front of the level's hash launch.  The fused form would be sound -- a node is either in the list or read as an
+// absent child, so a probe never looks for a key that a claim of the same launch inserts, and a claimed slot it walks over holds another
+// key whenever it is read -- but it would save one latency-shaped launch per level and put the claim's registers into the hash kernel;
+// the separate launch needs no argument at all.  Capacity, bounds, the counts' download and the error word are the update's: the same
+// smt_settle_capacity before the first writing launch, the same bound, the same smt_queue_counts behind the last.
 #include "merkle_plan.hpp"
 #include "../../include/fawkes_hip_sparse_merkle.h"
+#include "../../include/fawkes_hip_merkle_set.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
 
@@ -382,6 +392,43 @@ static int smt_update_args(fk_ctx *ctx, const fk_smt *t, size_t k) {
     return FK_OK;
 }
 
+// a level as merkle_plan.hpp's bulk write sees it
+struct SmtStore {
+    uint64_t *keys; Fr *vals; uint32_t log_cap; const Fr *zero_l; unsigned long long *count, *err;
+    __device__ __forceinline__ void put(uint64_t key, const Fr &v) const {
+        const uint64_t s = smt_claim(keys, log_cap, key, count, err);
+        if (s != SMT_NOT_FOUND) vals[s] = v;
+    }
+    __device__ __forceinline__ const Fr *get(uint64_t key) const {
+        const uint64_t s = smt_find(keys, log_cap, key, err);
+        return s != SMT_NOT_FOUND ? vals + s : zero_l;
+    }
+};
+
+// k >= 1, arguments checked, the staging claimed.  timed: null, or what the timed entry wants (then the call waits for the stream)
+static int smt_set_dev(fk_ctx *ctx, fk_smt *t, const uint64_t *d_idx, const Fr *d_leaves, uint32_t k, Fr *d_root, const MsTimed *timed) {
+    const uint32_t depth = t->depth;
+    FK_TRY(smt_take_counts(ctx, t, false));
+    FK_TRY(smt_usable(ctx, t));
+    // the indices first: nothing is written, and no table grows, before they are known to be good
+    PosDev d; FK_TRY(misc_head(ctx, nullptr, nullptr, 0, &d));
+    FK_TRY(ms_check_indices(ctx, d.flag, d_idx, k, depth, "sparse merkle"));
+    if (depth == 0) return ms_set_depth0(ctx, d_leaves, k, t->d_root, d_root, timed);
+
+    MsScratch s; FK_TRY(ms_reserve(ctx, d_idx, depth, k, &s));
+    FK_TRY(smt_settle_capacity(ctx, t, k));
+    MuEvents tm;
+    if (timed) FK_HIP(ctx, tm.make(2 + 2 * (size_t)depth));
+    // from here on the tables may hold up to this much more
+    for (uint32_t l = 0; l < depth; l++) t->lv[l].bound += ms_level_bound(depth, l, k);
+    unsigned long long *err = t->d_meta + SMT_META_ERR;
+    auto store_at = [&](uint32_t l) { const fk_smt::Level &v = t->lv[l]; return SmtStore{v.keys, v.vals, v.log_cap, t->d_zero + l, t->d_meta + l, err}; };
+    FK_TRY(ms_set_levels(ctx, (const Fr *)t->d_tab, t->h.f, t->h.p, depth, d_idx, d_leaves, k, s, store_at, t->d_root, d_root, timed ? &tm : nullptr));
+    FK_TRY(smt_queue_counts(ctx, t));
+    if (timed) FK_TRY(ms_finish_timed(ctx, tm, depth, s, *timed));
+    return FK_OK;
+}
+
 // n >= 1, arguments checked.  Read only: the tables, `misc` for the flag
 static int smt_proofs_dev(fk_ctx *ctx, const fk_smt *t, const uint64_t *d_idx, size_t n, Fr *d_leaves, Fr *d_sib) {
     const uint32_t depth = t->depth;
@@ -617,6 +664,52 @@ int fk_smt_export_level(fk_ctx *ctx, const fk_smt *t, uint32_t level, uint64_t *
     FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < have.size(); i++) { keys[i] = have[i].first; fr_to_limbs(hv[have[i].second], vals + 4 * i); }
     return FK_OK;
+}); }
+
+// ---- include/fawkes_hip_merkle_set.h
+int fk_smt_set_timed_dev(fk_ctx *ctx, fk_smt *t, const void *d_indices, const void *d_leaves, size_t k, void *d_root, double ms[2], uint64_t *distinct) {
+    return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    FK_TRY(smt_update_args(ctx, t, k));
+    if (ms) ms[0] = ms[1] = 0;
+    if (!k) return FK_OK;
+    if (!d_indices || !d_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_TRY(scratch_claim(ctx, "sparse merkle set"));      // merkle_plan.hpp's bulk write sorts and selects in stage_a/b/c
+    const MsTimed timed{ms, distinct};
+    return smt_set_dev(ctx, t, (const uint64_t *)d_indices, (const Fr *)d_leaves, (uint32_t)k, (Fr *)d_root, &timed);
+}); }
+
+int fk_smt_set_dev(fk_ctx *ctx, fk_smt *t, const void *d_indices, const void *d_leaves, size_t k, void *d_root) { return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    FK_TRY(smt_update_args(ctx, t, k));
+    if (!k) return FK_OK;
+    if (!d_indices || !d_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_TRY(scratch_claim(ctx, "sparse merkle set"));
+    return smt_set_dev(ctx, t, (const uint64_t *)d_indices, (const Fr *)d_leaves, (uint32_t)k, (Fr *)d_root, nullptr);
+}); }
+
+int fk_smt_set(fk_ctx *ctx, fk_smt *t, const uint64_t *indices, const uint64_t *leaves, size_t k, uint64_t root[4]) { return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    FK_TRY(smt_update_args(ctx, t, k));
+    if (!k) return FK_OK;
+    if (!indices || !leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    FK_TRY(scratch_claim(ctx, "sparse merkle set"));
+    // one block: leaves | the root | indices
+    const size_t ib = k * sizeof(uint64_t), lb = k * sizeof(Fr);
+    MuDevBlock blk;
+    FK_HIP(ctx, hipMalloc(&blk.p, lb + sizeof(Fr) + ib));
+    Fr *d_leaves = (Fr *)blk.p, *d_root = d_leaves + k;
+    uint64_t *d_idx = (uint64_t *)(d_root + 1);
+    FK_HIP(ctx, hipMemcpyAsync(d_idx, indices, ib, hipMemcpyHostToDevice, ctx->stream));
+    FK_HIP(ctx, hipMemcpyAsync(d_leaves, leaves, lb, hipMemcpyHostToDevice, ctx->stream));
+    int rc = smt_set_dev(ctx, t, d_idx, d_leaves, (uint32_t)k, root ? d_root : nullptr, nullptr);
+    if (rc == FK_OK && root) {
+        auto down = [&]() -> int { FK_HIP(ctx, hipMemcpyAsync(root, d_root, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream)); return FK_OK; };
+        rc = down();
+    }
+    (void)hipStreamSynchronize(ctx->stream);      // the block is in use until the stream has drained, on the error paths too
+    if (rc == FK_OK) { rc = smt_take_counts(ctx, t, false); if (rc == FK_OK) rc = smt_usable(ctx, t); }      // the counts have arrived with the root
+    return rc;
 }); }
 
 }  // extern "C"

@@ -5,7 +5,9 @@ which only the nodes ever written are stored -- the account tree of a rollup (de
 An untouched subtree at level l has the value defaults[l] (defaults[0] = 0, defaults[l + 1] = H(defaults[l], defaults[l])): what a
 dense tree gives its zero padding, so a `SparseMerkleTree` and a `MerkleTree` over the same leaves agree on every root and sibling.
 `update` is `merkle.update`'s contract (k leaf writes IN ORDER -> merkle.MerkleUpdates); `proofs` reads without changing anything;
-`leaves()` is how a tree is saved: a new tree given them through `update` has the same root.
+`leaves()` is how a tree is saved: `SparseMerkleTree.restore(ctx, params, depth, *tree.leaves())` is a new tree with the same root and
+the same stored nodes (merkle_set.py: one bulk write, one hash per node).  `set` is that bulk write on its own: the final state of
+`update`, the new root and no proofs.
 
 The C prototypes of these entry points live in this module's own table (the table of _abi.py mirrors fawkes_hip.h and nothing else).
 Limits: one GPU; at most 2^28 writes per call; entries are never removed (a leaf written back to 0 stays stored).
@@ -109,7 +111,7 @@ class SparseMerkleTree(api._Handle):
         return dict(zip((int(x) for x in keys), _fr_ints(vals)))
 
     def leaves(self):
-        """(indices, values) of the stored leaves ascending by index: given to `update` of a new tree they restore the root"""
+        """(indices, values) of the stored leaves ascending by index: given to `restore` they make a new tree with the same root"""
         lv = self.level(0)
         return list(lv), list(lv.values())
 
@@ -156,3 +158,20 @@ class SparseMerkleTree(api._Handle):
             return MerkleUpdates(root, old, sib, roots)
         flat = _fr_ints(sib)
         return MerkleUpdates(_fr_ints(root)[0], _fr_ints(old), [flat[j * depth:(j + 1) * depth] for j in range(k)], _fr_ints(roots))
+
+    # ---- bulk writes (merkle_set.py, imported where it is used: that module imports this one's class)
+    def set(self, indices, leaves):
+        """merkle_set.set_sparse: the final state of `update(indices, leaves)`, one hash per touched node -> the new root"""
+        from . import merkle_set
+        return merkle_set.set_sparse(self, indices, leaves)
+
+    def set_dev(self, d_indices, d_leaves, k, d_root=None):
+        """merkle_set.set_sparse_dev: everything in device memory; d_root may be None"""
+        from . import merkle_set
+        merkle_set.set_sparse_dev(self, d_indices, d_leaves, k, d_root)
+
+    @classmethod
+    def restore(cls, ctx, params, depth, indices, leaves, expected_leaves=0):
+        """merkle_set.restore: a new tree given its leaves by one `set`"""
+        from . import merkle_set
+        return merkle_set.restore(ctx, params, depth, indices, leaves, expected_leaves)

@@ -11,7 +11,8 @@
  * replaced, its depth siblings as of its own moment (siblings[j * depth + l], leaf level first) and the root after it.  One launch of k
  * hashes per level whatever the collisions among the indices.  fk_smt_proofs* reads: the stored (or default) leaf and siblings of any
  * index, nothing is changed.  fk_smt_export_level lists what a level stores; level 0 is how a tree is saved: a new tree given the
- * exported leaves through fk_smt_update has the same root.
+ * exported leaves has the same root -- through the bulk write of fawkes_hip_merkle_set.h, which hashes every node once and returns no
+ * proofs (the ordered update here restores the same tree at depth hashes per leaf).
  *
  * Conventions: field elements are Montgomery limbs (4 x u64) as everywhere; any output may be NULL; k = 0 (n = 0) touches nothing.
  * Refusals (FK_ERR_BAD_ARG), all before a byte of the tree or of an output is written: parameters with t != 3; depth > FK_SMT_MAX_DEPTH;
