@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <map>
+#include <mutex>
 #include <string>
 #include <new>
 #include <stdexcept>
@@ -63,6 +64,13 @@ struct MsmLane {
     DevBuf digits, sorted, totals, starts, perm, overlist, tasktab, partials, s2_cnt1, s2_seg, s2_cnt2, s2_tmp_idx, s2_tmp_lo, buckets;
     DevBuf buckets2;     // the buckets of a multiplication that reuses this lane's sort (B2 after B1): its accumulation is queued right behind B1's, before B1's tail has read `buckets`
     const void *last_sort_scalars = nullptr; size_t last_sort_n = 0; unsigned last_sort_c = 0; bool last_merged = false;   // what `sorted` currently holds
+    // This lane's sort LENT to a multiplication on another lane (A adopts L's, msm_begin's `lender`): the borrower's kernels read sorted, starts,
+    // totals, perm, the MsmDyn record and the task tables from here.  lent_pending: borrowers whose accumulation is not queued yet (deferred
+    // pieces); ev_lent: recorded on the borrower's lane behind the last kernel that reads them (queue_accumulate) -- this lane waits for it before it sorts again or
+    // grows a buffer.
+    hipEvent_t ev_lent = nullptr;
+    bool lent_valid = false;
+    int lent_pending = 0;
     // ... the oversized-bucket state and tables that belong to it live on the device (msm.hip: MsmDyn, tasktab)
 };
 
@@ -75,7 +83,7 @@ struct MsmTail {
     size_t h_cap = 0;
     DevBuf d_wp;
 };
-static constexpr int MSM_TAILS = 12;     // five per proof; a second proof's four witness multiplications may be begun before the first one's are collected (early front)
+static constexpr int MSM_TAILS = 12;     // five per proof, six where A is begun in two parts (A adopts L's sort); a second proof's four or five witness multiplications may be begun before the first one's are collected (early front)
 static constexpr int MSM_LANES = 4;   // B pair, L, A and H each on a lane of their own in the sorts-first schedule (prover.hip)
 
 // Which variables feed the A and the B query, as index lists (they are structural: a resident constraint system
@@ -83,6 +91,8 @@ static constexpr int MSM_LANES = 4;   // B pair, L, A and H each on a lane of th
 struct QueryIdx {
     const uint32_t *a = nullptr, *b = nullptr;                                 // variable indices, query order
     uint64_t n_a = 0, n_b = 0;
+    uint64_t a_fp = 0;                                                         // fingerprint of the A list, computed on the device when the system is loaded (query_fingerprint)
+    bool a_fp_valid = false;
 };
 
 // ---- what ONE run of the prover is given besides key and vectors.  These are arguments, handed down the calls: nothing of them is kept in
@@ -137,8 +147,8 @@ struct fk_ctx : fk::CtxScratch {
     // Early front (pipelined proofs, sorts-first schedule): while proof k's last kernels run -- latency-bound tails that leave the GPU
     // mostly idle -- the memory-bound front of proof k+1 (evaluation of a, b, c and the witness sorts) is already queued behind
     // proof k's last accumulation (ProveRun::before_block queues it).  early: what that front left for proof k+1's run to pick up.
-    struct EarlyFront { bool done = false; int tails[4] = {-1, -1, -1, -1}; const fk_key *key = nullptr; const struct fk_r1cs_dev *r1cs = nullptr; const void *d_z = nullptr; } early;
-    int wit_tail[4] = {-1, -1, -1, -1}; // B1, B2, L, A
+    struct EarlyFront { bool done = false; int tails[5] = {-1, -1, -1, -1, -1}; const fk_key *key = nullptr; const struct fk_r1cs_dev *r1cs = nullptr; const void *d_z = nullptr; } early;
+    int wit_tail[5] = {-1, -1, -1, -1, -1}; // B1, B2, L, A, A's inputs (only when A adopts L's sort: A is then the aux part alone)
     // witness hand-over from host memory (fk_witness_upload_async / fk_prove_r1cs_submit): two device slots filled on a copy
     // stream of their own, so that the upload of proof k+1's witness runs underneath proof k
     hipStream_t copy_st = nullptr;
@@ -174,6 +184,17 @@ struct fk_key {
     fk::G1Affine alpha_g1, beta_g1, delta_g1;
     fk::G2Affine beta_g2, delta_g2;
     fk::KeyPre pre_h, pre_l, pre_a, pre_b1, pre_b2;       // optional (memory permitting), see key_precompute
+    // A's aux bases in L's index space (msm.hip: key_a_pad): d[j] = A's base of aux variable j if that variable occurs in the A query, else
+    // the point at infinity -- so that A's aux part is a multiplication over L's scalars and adopts L's bucket sort (prover.hip:
+    // witness_begin).  One per A query of a resident constraint system (fp: QueryIdx::a_fp), at most A_PADS of them, built by the first proof
+    // that meets the query.  Several contexts may prove from one key at the same time (fawkes_hip.h), so: slots are found and filled under
+    // a_pad_mu, a filled slot is never changed or freed by a proof (only by key_pre_free, i.e. fk_key_free / _drop_levels / _derive_levels,
+    // which are not called while proofs are in flight), and the key's own arrays and levels are not touched.  refused: that query's array
+    // did not fit, or a and l were in different forms: not tried again.  A query that finds no slot keeps A's own sort.
+    struct APad { fk::G1Affine *d = nullptr; fk::KeyPre pre; uint64_t n_a = 0, n_l = 0, fp = 0; bool used = false, refused = false; };
+    static constexpr int A_PADS = 2;
+    mutable APad a_pad[A_PADS];
+    mutable std::mutex a_pad_mu;
     double load_s[2] = {0, 0};                            // seconds the loader spent on the arrays (transfer, conversion, checks / derivation) and on the fixed-base levels
 };
 
@@ -219,6 +240,7 @@ static inline bool proof_holds_staging(const fk_ctx *ctx) { return ctx->early.do
 // The MSM lanes: the above, or witness multiplications begun and not collected (fk_prove_msms_z_begin_dev .. _finish_dev) with whatever of
 // them is still deferred (deferred_tails is filled and drained together with deferred).
 static inline bool proof_holds_lanes(const fk_ctx *ctx) {
+    for (const MsmLane &ln : ctx->lanes) if (ln.lent_pending) return true;      // a borrowed sort whose borrower is not queued yet (it is one of the deferred pieces)
     return proof_holds_staging(ctx) || ctx->wit_active || !ctx->deferred.empty() || !ctx->deferred_tails.empty();
 }
 
@@ -300,7 +322,7 @@ struct RoctxRange {
 
 // Tuning knobs.  A release build compiles the measured default in; `make EXP=1` (-DFK_EXPERIMENTS, libfawkes_hip_exp.so, loaded
 // with FK_LIB_VARIANT=exp) reads them from the environment for same-box A/B runs.  The run-time switches of a release build
-// are few and documented in DESIGN.md: FK_DEBUG, FK_MSM_PRECOMP, FK_MSM_PRE_MIN_LOG2, FK_PROVE_SORTS_FIRST, FK_SPMV_BIN_MIN, FK_SPMV_DEDUP,
+// are few and documented in DESIGN.md: FK_DEBUG, FK_MSM_PRECOMP, FK_MSM_PRE_MIN_LOG2, FK_PROVE_SORTS_FIRST, FK_PROVE_SHARE_AL_SORT, FK_SPMV_BIN_MIN, FK_SPMV_DEDUP,
 // FK_OVERLAP_WITNESS, FK_MULTI_HOST_EVENTS.
 static inline int tune(const char *name, int dflt) {
 #ifdef FK_EXPERIMENTS
@@ -409,11 +431,20 @@ int msm_g1_dev(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t
 // ready: event after which bases / scalars are valid (nullptr: everything queued on ctx->stream so far)
 // pre: the bases' precomputed levels (nullptr / empty / made for another n: the ordinary W-bucket-set path)
 // defer: queue only the front (digits, sort, size ordering); msm_run_deferred queues the rest (fk_ctx::deferred)
-int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr, bool defer = false);
+// uncounted: a small first part of the multiplication begun next (A's inputs before A's aux part): the accumulation statistics count the pair once
+int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr, bool defer = false, bool uncounted = false);
+// the same multiplication over the scalars lane `lender` has just sorted (same pointer, n and plan): no digits, no sort -- it reads the
+// lender's sort products and owns only its buckets and partials, on lane `lane` (that lane's second bucket buffer), which is not the
+// lender's.  *adopted = false: the lender holds no such sort, nothing was queued.
+int msm_g1_begin_adopt(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int lender, int lane, bool *adopted, int *tail, const KeyPre *pre = nullptr, bool defer = false);
 int msm_g1_end(fk_ctx *ctx, int tail, G1Xyzz *out);
 int msm_g2_begin(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail, hipEvent_t ready = nullptr, const KeyPre *pre = nullptr, bool defer = false);
 // fills key->pre_* for the slices the key holds (FK_MSM_PRECOMP=0 disables; skipped silently when HBM is short); key_pre_free undoes
 int key_precompute(fk_ctx *ctx, fk_key *key);
+// A's aux bases padded into L's index space for the A query `qi` (fk_key::a_pad): *pad = the array to multiply against where the shared A / L
+// sort applies to this key and query, else null.  The first proof that meets a query builds it: its host thread waits, others wait for it.
+int key_a_pad(fk_ctx *ctx, const fk_key *key, const QueryIdx *qi, const fk_key::APad **pad);
+int query_fingerprint(fk_ctx *ctx, const uint32_t *d_idx, size_t n, uint64_t *out);     // order-sensitive 64-bit digest of an index list, computed on the device
 int key_levels_headroom(fk_ctx *ctx, const fk_key *key, int64_t *bytes);
 void key_pre_free(fk_key *key);
 int msm_g2_end(fk_ctx *ctx, int tail, G2Xyzz *out);
@@ -422,7 +453,7 @@ int msm_run_deferred(fk_ctx *ctx, hipEvent_t after);
 int upload_deferred(fk_ctx *ctx, bool gate_on_main);      // queues the witness uploads fk_prove_r1cs_submit left for later
 int witness_slot_reserve(fk_ctx *ctx, int slot, size_t bytes, bool *moved = nullptr);      // prover.hip: room for `bytes` in a witness slot (+ its stream and events)
 // prover.hip: the prover behind the extern "C" entries, with what a run is given as arguments (ProveRun)
-int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q, int tails_out[4]);
+int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q, int tails_out[5]);
 bool early_front_applies(const fk_key *key);
 int witness_queries_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q);      // fk_prove_msms_z_begin_dev
 int witness_queries_finish(fk_ctx *ctx, const fk_key *key, const void *d_h_slice, uint8_t out[FK_MSM_RESULT_BYTES]);      // fk_prove_msms_finish_dev

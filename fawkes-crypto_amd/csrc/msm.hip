@@ -996,6 +996,7 @@ int streams_init(fk_ctx *ctx) {
         FK_HIP(ctx, hipStreamCreateWithFlags(&ln.st, hipStreamNonBlocking));
         FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_in, hipEventDisableTiming));
         FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_sorted, hipEventDisableTiming));
+        FK_HIP(ctx, hipEventCreateWithFlags(&ln.ev_lent, hipEventDisableTiming));
     }
     // (events take no part in that mapping: the ones every proof records come with the streams, so that no caller creates one on demand)
     for (hipEvent_t *e : {&ctx->ev_main, &ctx->ev_z, &ctx->ev_upload_gate}) if (!*e) FK_HIP(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -1011,6 +1012,17 @@ static int pinned_reserve(fk_ctx *ctx, void **p, size_t *cap, size_t bytes, size
     return FK_OK;
 }
 
+// Before a lane overwrites, grows or frees the products of its sort: a multiplication on another lane that adopted them (MsmLane::ev_lent)
+// must have read them.  host_wait: the host waits (a buffer is about to be freed); otherwise the lane's stream does.
+static int lane_reclaim(fk_ctx *ctx, MsmLane &ln, bool host_wait) {
+    if (ln.lent_pending) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: this lane's sort is lent to a multiplication whose accumulation has not been queued yet");
+    if (!ln.lent_valid) return FK_OK;
+    if (host_wait) FK_HIP(ctx, hipEventSynchronize(ln.ev_lent));
+    else FK_HIP(ctx, hipStreamWaitEvent(ln.st, ln.ev_lent, 0));
+    ln.lent_valid = false;      // (a stream wait is enough from here on: whatever frees a buffer of this lane synchronises its stream first)
+    return FK_OK;
+}
+
 // What the stages of one multiplication share: msm_begin fills it in, msm_reserve binds the pointers into the lane's scratch, the
 // deferred pieces (msm_begin's `defer`) keep a copy.
 template <class F>
@@ -1023,7 +1035,9 @@ struct MsmJob {
     const Fr *scalars;
     size_t n, WB, max_tasks, max_tiles, wp_bytes;
     uint32_t WR;                        // bucket sets to reduce
-    bool merged, have_sort;             // have_sort: the lane's previous sort is reused (B2 after B1)
+    bool merged, have_sort;             // have_sort: the lane's previous sort is reused (B2 after B1), or another lane's is adopted (lender)
+    MsmLane *lender;                    // the lane whose sort this multiplication reads (A's aux part adopts L's), else null
+    bool uncounted;                     // a small first part of the multiplication that follows (A's inputs): the statistics count the pair as one accumulation
     MsmDyn *dyn;                        // device-side state of this lane's sort
     uint32_t *digits, *sorted, *totals, *starts, *perm;
     Task *tasks;
@@ -1051,6 +1065,29 @@ static int msm_reserve(MsmJob<F> &j) {
     const size_t max_tiles = j.max_tiles = (size_t)p.W * ((n + S2_TILE - 1) / S2_TILE) + nseg + 1;
     // Growing a buffer frees the old one: everything queued on this lane must be finished first.
     struct Need { DevBuf *b; size_t bytes; };
+    if (j.lender) {
+        // An adopted sort: the lane holds this multiplication's buckets (its second set: the multiplication before it on this lane may not
+        // have reduced the first yet) and the partial sums of its oversized buckets; every table of the sort is the lender's, bound as the
+        // lender's own multiplication bound them (same n, same plan, hence the same offsets).
+        MsmLane &ld = *j.lender;
+        const Need mine[] = {{&ln.buckets2, WB * sizeof(Xyzz<F>)}, {&ln.partials, max_tasks * sizeof(Xyzz<F>)}};
+        bool grow_mine = false;
+        for (const Need &nd : mine) grow_mine = grow_mine || nd.bytes > nd.b->cap;
+        if (grow_mine) {
+            FK_HIP(ctx, hipStreamSynchronize(ln.st));
+            for (const Need &nd : mine) FK_HIP(ctx, nd.b->reserve(nd.bytes));
+        }
+        FK_HIP(ctx, tl.d_wp.reserve(wp_dev_bytes));
+        FK_TRY(pinned_reserve(ctx, &tl.h_wp, &tl.h_cap, j.wp_bytes, 16));
+        j.dyn = (MsmDyn *)((char *)ld.overlist.p + OVER_MAX * sizeof(OverEntry));
+        j.tasks = ld.tasktab.as<Task>();
+        j.obs = (OverBucket *)((char *)ld.tasktab.p + ((max_tasks * sizeof(Task) + 15) & ~(size_t)15));
+        j.digits = nullptr; j.sorted = ld.sorted.as<uint32_t>();
+        j.totals = ld.totals.as<uint32_t>(); j.starts = ld.starts.as<uint32_t>();
+        j.winparts = tl.d_wp.as<Xyzz<F>>();
+        j.perm = ld.perm.as<uint32_t>();
+        return FK_OK;
+    }
     const Need needs[] = {
         {&ln.digits, (size_t)p.W * n * 4}, {&ln.sorted, (size_t)p.W * n * 4}, {&ln.totals, WB * 4}, {&ln.starts, WB * 4},
         {&ln.perm, WB * 4 + SIZE_BINS * 4}, {&ln.overlist, OVER_MAX * sizeof(OverEntry) + sizeof(MsmDyn) + 64}, {j.have_sort ? &ln.buckets2 : &ln.buckets, WB * sizeof(Xyzz<F>)},
@@ -1060,6 +1097,7 @@ static int msm_reserve(MsmJob<F> &j) {
     bool grow = false;
     for (const Need &nd : needs) grow = grow || nd.bytes > nd.b->cap;
     if (grow) {
+        FK_TRY(lane_reclaim(ctx, ln, /*host_wait=*/true));
         FK_HIP(ctx, hipStreamSynchronize(ln.st));
         for (const Need &nd : needs) FK_HIP(ctx, nd.b->reserve(nd.bytes));
         if (!j.have_sort) ln.last_sort_scalars = nullptr;
@@ -1167,6 +1205,9 @@ static int queue_size_order(const MsmJob<F> &j) {
 template <class F>
 static Xyzz<F> *bucket_buf(const MsmJob<F> &j) { return (j.have_sort ? j.ln->buckets2 : j.ln->buckets).template as<Xyzz<F>>(); }
 
+template <class F>
+static int queue_overflow(const MsmJob<F> &j);
+
 // The back of a multiplication, first piece: the bucket accumulation.  MINW: msm_accumulate_kernel.
 template <class F>
 static int queue_accumulate(MsmJob<F> j) {
@@ -1176,7 +1217,7 @@ static int queue_accumulate(MsmJob<F> j) {
     constexpr int MINW = std::is_same<F, Fq>::value ? 4 : 2;
     Xyzz<F> *buckets = bucket_buf(j);
     std::vector<EventPair> &evv = (sizeof(F) == sizeof(Fq)) ? ctx->ev_acc : ctx->ev_acc2;
-    FK_TRY(stats_begin(ctx, evv, (uint64_t)j.n, st));
+    if (!j.uncounted) FK_TRY(stats_begin(ctx, evv, (uint64_t)j.n, st));
     if (j.merged)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_merged_kernel<F, MINW>), dim3((p.B + 255) / 256), dim3(256), 0, st, j.bases, j.lev, j.sorted, j.n,
                            j.starts, j.totals, p.B, p.W, j.dyn, j.perm, j.perm + p.B, buckets);
@@ -1184,38 +1225,61 @@ static int queue_accumulate(MsmJob<F> j) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_accumulate_kernel<F, MINW>), dim3((unsigned)((j.WB + 255) / 256)), dim3(256), 0, st, j.bases, j.sorted, j.n,
                            j.starts, j.totals, p.B, p.W, j.dyn, j.perm, buckets);
     FK_HIP(ctx, hipGetLastError());
-    FK_TRY(stats_end(ctx, evv, st));
+    if (!j.uncounted) FK_TRY(stats_end(ctx, evv, st));
     if (!ctx->ev_acc_done) FK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_acc_done, hipEventDisableTiming));
     FK_HIP(ctx, hipEventRecord(ctx->ev_acc_done, st)); ctx->ev_acc_done_valid = true;
     FK_DBG_ST(ctx, st, "msm_accumulate");
+    if (j.lender) {
+        // An adopted sort: the oversized buckets -- the last kernels that read the lender's tables -- go right behind the accumulation instead of
+        // into the tail, and the lender gets its sort back here.  The tail may be queued much later, and behind other lanes' long tails where
+        // HIP maps both streams onto one hardware queue: the lender's next sort (the next proof's early front) must not wait for that.
+        FK_TRY(queue_overflow<F>(j));
+        // the additions counter and the error word of the lender's record, as B2 reports B1's (the padded entries count as additions here)
+        FK_HIP(ctx, hipMemcpyAsync((char *)j.tl->h_wp + j.wp_bytes, &j.dyn->adds, 8, hipMemcpyDeviceToHost, st));
+        FK_HIP(ctx, hipMemcpyAsync((char *)j.tl->h_wp + j.wp_bytes + 8, &j.dyn->error, 4, hipMemcpyDeviceToHost, st));
+        FK_HIP(ctx, hipEventRecord(j.lender->ev_lent, st));
+        j.lender->lent_valid = true;
+        if (j.lender->lent_pending > 0) j.lender->lent_pending--;
+    }
     return FK_OK;
 }
 
-// ... second piece, the tail: oversized buckets, bucket reduction, download of the window sums
+// oversized buckets: fixed grids looping over the device-built tables (they leave at once when there is nothing to do)
+template <class F>
+static int queue_overflow(const MsmJob<F> &j) {
+    using FC = typename ColdOf<F>::type;   // layout-identical field with an out-of-line multiply
+    fk_ctx *ctx = j.ctx;
+    MsmLane &ln = *j.ln;
+    hipStream_t st = ln.st;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_kernel<F, FC>), dim3(2048), dim3(64), 0, st,
+                       j.bases, j.lev, j.sorted, j.n, j.starts, j.totals, j.p.B, j.dyn, j.tasks, ln.partials.as<Xyzz<FC>>());
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_overflow");
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_fold_kernel<F>), dim3(256), dim3(256), 0, st, j.obs, j.dyn, ln.partials.as<Xyzz<F>>(), bucket_buf(j));
+    FK_HIP(ctx, hipGetLastError());
+    FK_DBG_ST(ctx, st, "msm_overflow_fold");
+    return FK_OK;
+}
+
+// ... second piece, the tail: oversized buckets (an adopted sort's went behind its accumulation), bucket reduction, download of the window sums
 template <class F>
 static int queue_tail(MsmJob<F> j) {
-    using FC = typename ColdOf<F>::type;   // layout-identical field with an out-of-line multiply
     fk_ctx *ctx = j.ctx;
     const MsmPlan &p = j.p;
     MsmLane &ln = *j.ln;
     MsmTail &tl = *j.tl;
     hipStream_t st = ln.st;
     Xyzz<F> *buckets = bucket_buf(j);
-    // oversized buckets: fixed grids looping over the device-built tables (they leave at once when there is nothing to do)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_kernel<F, FC>), dim3(2048), dim3(64), 0, st,
-                       j.bases, j.lev, j.sorted, j.n, j.starts, j.totals, p.B, j.dyn, j.tasks, ln.partials.as<Xyzz<FC>>());
-    FK_HIP(ctx, hipGetLastError());
-    FK_DBG_ST(ctx, st, "msm_overflow");
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_overflow_fold_kernel<F>), dim3(256), dim3(256), 0, st, j.obs, j.dyn, ln.partials.as<Xyzz<F>>(), buckets);
-    FK_HIP(ctx, hipGetLastError());
-    FK_DBG_ST(ctx, st, "msm_overflow_fold");
+    if (!j.lender) FK_TRY(queue_overflow<F>(j));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_bucket_reduce_kernel<F>), dim3(p.nblk, j.WR), dim3(256), 0, st, buckets, p.B, p.L, p.T, p.nblk, j.winparts);
     Xyzz<F> *folded = j.winparts + (size_t)j.WR * p.nblk;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_fold_partials_kernel<F>), dim3(j.WR), dim3(256), 0, st, j.winparts, p.nblk, folded);
     FK_HIP(ctx, hipGetLastError());
     FK_HIP(ctx, hipMemcpyAsync(tl.h_wp, folded, j.wp_bytes, hipMemcpyDeviceToHost, st));
-    FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + j.wp_bytes, &j.dyn->adds, 8, hipMemcpyDeviceToHost, st));
-    FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + j.wp_bytes + 8, &j.dyn->error, 4, hipMemcpyDeviceToHost, st));
+    if (!j.lender) {     // (an adopted sort's record was copied behind its accumulation: the lender has its sort back by now)
+        FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + j.wp_bytes, &j.dyn->adds, 8, hipMemcpyDeviceToHost, st));
+        FK_HIP(ctx, hipMemcpyAsync((char *)tl.h_wp + j.wp_bytes + 8, &j.dyn->error, 4, hipMemcpyDeviceToHost, st));
+    }
     FK_HIP(ctx, hipEventRecord(tl.done, st));
     FK_DBG_ST(ctx, st, "msm_bucket_reduce");
     return FK_OK;
@@ -1237,8 +1301,10 @@ static void lanes_advance(fk_ctx *ctx, int li, bool defer = false) {
 // the first proof of a size).  The five multiplications of a proof are therefore in the lanes' queues microseconds after
 // the quotient's kernels, and the GPU decides what runs underneath what.
 template <class F>
-static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail_out, hipEvent_t ready, const KeyPre *pre = nullptr, bool defer = false) {
+static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail_out, hipEvent_t ready, const KeyPre *pre = nullptr, bool defer = false,
+                     int lender_li = -1, int own_li = -1, bool *adopted = nullptr, bool uncounted = false) {
     *tail_out = -1;
+    if (adopted) *adopted = false;
     if (n == 0) return FK_OK;
     if (n >= ((size_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: n too large");
     int ti = -1;
@@ -1257,11 +1323,23 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
     // during which nothing else ran: 31 % of the proof).
     MsmLane &prev = ctx->lanes[ctx->lane_prev];
     const bool have_sort = reuse_sort && prev.st && prev.last_sort_scalars == (const void *)d_scalars && prev.last_sort_n == n && prev.last_sort_c == p.c && prev.last_merged == merged;
-    const int li = have_sort ? ctx->lane_prev : ctx->lane_next;
+    // ... or adopts the sort of ANOTHER lane (A's aux part after L): it goes on lane own_li behind what is queued there (A's inputs), takes that
+    // lane's second bucket buffer and reads the lender's tables; the rotation of the lanes is left alone.  The lender must hold exactly this sort; if not, nothing is queued and the caller takes its ordinary path.
+    MsmLane *lender = nullptr;
+    if (lender_li >= 0) {
+        if (lender_li >= MSM_LANES || own_li < 0 || own_li >= MSM_LANES) return FK_OK;
+        MsmLane &ld = ctx->lanes[lender_li];
+        if (lender_li == own_li || !ld.st || !ctx->lanes[own_li].st || ld.last_sort_scalars != (const void *)d_scalars || ld.last_sort_n != n ||
+            ld.last_sort_c != p.c || ld.last_merged != merged) return FK_OK;
+        lender = &ld;
+        *adopted = true;
+    }
+    const int li = lender ? own_li : (have_sort ? ctx->lane_prev : ctx->lane_next);
     MsmLane &ln = ctx->lanes[li];
     if (!ln.st) FK_SET_ERR(ctx, FK_ERR_HIP, "msm: the context's streams were not created");      // (streams_init: fk_init, fk_trim)
-    lanes_advance(ctx, li, defer);
-    if (ready) FK_HIP(ctx, hipStreamWaitEvent(ln.st, ready, 0));      // (the front of the multiplication runs on the lane's stream as well)
+    if (!lender) lanes_advance(ctx, li, defer);
+    if (lender) FK_HIP(ctx, hipStreamWaitEvent(ln.st, lender->ev_sorted, 0));      // recorded behind the lender's size ordering; the scalars themselves are not read
+    else if (ready) FK_HIP(ctx, hipStreamWaitEvent(ln.st, ready, 0));      // (the front of the multiplication runs on the lane's stream as well)
     else {
         FK_HIP(ctx, hipEventRecord(ln.ev_in, ctx->stream));        // scalars / bases produced on the main stream
         FK_HIP(ctx, hipStreamWaitEvent(ln.st, ln.ev_in, 0));
@@ -1269,10 +1347,12 @@ static int msm_begin(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars,
     MsmJob<F> job{};
     job.ctx = ctx; job.p = p; job.ln = &ln; job.tl = &tl;
     job.bases = d_bases; job.lev = merged ? (const Affine<F> *)pre->lev : nullptr; job.scalars = d_scalars;
-    job.n = n; job.merged = merged; job.have_sort = have_sort;
+    job.n = n; job.merged = merged; job.have_sort = have_sort || lender; job.lender = lender; job.uncounted = uncounted;
     FK_TRY(msm_reserve(job));
-    // With a reused sort (B2 after B1) the lane's state and tables are still valid.
-    if (!have_sort) {
+    // With a reused sort (B2 after B1) the lane's state and tables are still valid; an adopted one (A after L) is the lender's.
+    if (lender) lender->lent_pending++;       // until this multiplication's accumulation is queued (queue_accumulate)
+    else if (!have_sort) {
+        FK_TRY(lane_reclaim(ctx, ln, /*host_wait=*/false));
         FK_TRY(queue_sort(job));
         FK_TRY(queue_size_order(job));
         FK_HIP(ctx, hipEventRecord(ln.ev_sorted, ln.st)); ln.ev_sorted_valid = true;
@@ -1342,6 +1422,7 @@ void msm_abandon(fk_ctx *ctx) {
     if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
     for (int i = 0; i < MSM_TAILS; i++) ctx->tails[i].active = false;
     for (MsmLane &ln : ctx->lanes) { if (ln.st) (void)hipStreamSynchronize(ln.st); ln.last_sort_scalars = nullptr; }
+    for (MsmLane &ln : ctx->lanes) { ln.lent_pending = 0; ln.lent_valid = false; }      // every lane is idle: no borrower is left
 }
 
 void msm_release(fk_ctx *ctx) {
@@ -1359,6 +1440,7 @@ void msm_release(fk_ctx *ctx) {
             b->release();
         if (ln.ev_in) (void)hipEventDestroy(ln.ev_in);
         if (ln.ev_sorted) (void)hipEventDestroy(ln.ev_sorted);
+        if (ln.ev_lent) (void)hipEventDestroy(ln.ev_lent);
         if (ln.st) (void)hipStreamDestroy(ln.st);
         ln = MsmLane();
     }
@@ -1371,8 +1453,12 @@ void msm_release(fk_ctx *ctx) {
     }
 }
 
-int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready, const KeyPre *pre, bool defer) {
-    return msm_begin<Fq>(ctx, d_bases, d_scalars, n, false, tail, ready, pre, defer);
+int msm_g1_begin(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int *tail, hipEvent_t ready, const KeyPre *pre, bool defer, bool uncounted) {
+    return msm_begin<Fq>(ctx, d_bases, d_scalars, n, false, tail, ready, pre, defer, -1, -1, nullptr, uncounted);
+}
+int msm_g1_begin_adopt(fk_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int lender, int lane, bool *adopted, int *tail, const KeyPre *pre, bool defer) {
+    if (lender < 0 || lane < 0 || !adopted) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: no lender lane");
+    return msm_begin<Fq>(ctx, d_bases, d_scalars, n, false, tail, nullptr, pre, defer, lender, lane, adopted);
 }
 int msm_g1_end(fk_ctx *ctx, int tail, G1Xyzz *out) { return msm_end<Fq>(ctx, tail, out); }
 int msm_g2_begin(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, bool reuse_sort, int *tail, hipEvent_t ready, const KeyPre *pre, bool defer) {
@@ -1426,6 +1512,7 @@ static int msm_front_dump(fk_ctx *ctx, const Fr *d_scalars, size_t n, bool merge
     job.scalars = d_scalars; job.n = n; job.merged = merged;
     const MsmPlan &p = job.p;
     FK_TRY(msm_reserve(job));
+    FK_TRY(lane_reclaim(ctx, ln, /*host_wait=*/true));
     FK_TRY(queue_sort(job));
     FK_TRY(queue_size_order(job));
     ln.last_sort_scalars = nullptr;
@@ -1495,6 +1582,13 @@ static int precompute_levels(fk_ctx *ctx, const Affine<F> *d_bases, size_t n, Ke
 
 void key_pre_free(fk_key *k) {
     for (KeyPre *p : {&k->pre_h, &k->pre_l, &k->pre_a, &k->pre_b1, &k->pre_b2}) { if (p->lev) (void)hipFree(p->lev); *p = KeyPre(); }
+    // the padded A arrays go with the levels (they are in the form a and l had): the next proof builds what it needs again
+    std::lock_guard<std::mutex> lock(k->a_pad_mu);
+    for (fk_key::APad &c : k->a_pad) {
+        if (c.pre.lev) (void)hipFree(c.pre.lev);
+        if (c.d) (void)hipFree(c.d);
+        c = fk_key::APad();
+    }
 }
 
 // FK_MSM_PRECOMP: unset / 1 = derive the levels that fit (a skipped array leaves a warning in fk_last_error), 0 = none,
@@ -1613,6 +1707,114 @@ int key_precompute(fk_ctx *ctx, fk_key *k) {
                 if (k->pre_b1.lev && !k->pre_b2.lev) { (void)hipFree(k->pre_b1.lev); k->pre_b1 = KeyPre(); }
         }
     }
+    return FK_OK;
+}
+
+// ------------------------------------------------------------------------------------------ A's aux bases in L's index space
+// L multiplies the aux scalars z[v_in .. v_in + n_l) and A the inputs followed by the aux variables that occur in some A-side
+// combination -- most of them (95 % of the 1741-transaction system): A's bucket sort is L's done again in a compacted index space.
+// With A's aux bases laid out in L's index space (infinity where a variable does not occur; the walk of a bucket skips an infinite
+// base) A's aux part is a multiplication over L's scalars, reads L's sort (msm_begin: lender) and needs no gather, digits or sort.
+
+// digest of (position, index) pairs: a sum of mixed words, so the lanes may add in any order
+__global__ __launch_bounds__(256) void query_fingerprint_kernel(const uint32_t *idx, size_t n, unsigned long long *out) {
+    unsigned long long mine = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        unsigned long long z = ((unsigned long long)i << 32 | idx[i]) + 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        mine += z ^ (z >> 31);
+    }
+    const unsigned long long all = wave_sum_u64(mine);
+    if ((threadIdx.x & 63) == 0) atomicAdd(out, all);
+}
+int query_fingerprint(fk_ctx *ctx, const uint32_t *d_idx, size_t n, uint64_t *out) {
+    unsigned long long *d = nullptr;
+    FK_HIP(ctx, hipMalloc((void **)&d, 8));
+    unsigned long long h = 0;
+    hipError_t e = hipMemsetAsync(d, 0, 8, ctx->stream);
+    if (e == hipSuccess && n) {
+        hipLaunchKernelGGL(query_fingerprint_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, ctx->stream, d_idx, n, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    FK_HIP(ctx, e);
+    *out = (uint64_t)h + 0x5bd1e995u * (uint64_t)n;
+    return FK_OK;
+}
+
+// pad[idx[k] - v_in] = a[k] for the aux part of the A list, k in [v_in, n_a); the rest of pad was cleared (all-zero bytes = infinity).
+// An index outside L's range cannot come from a system that fits the key; it is dropped rather than written.
+__global__ __launch_bounds__(256) void a_pad_scatter_kernel(const G1Affine *a, const uint32_t *idx, size_t v_in, size_t n_a, size_t n_l, G1Affine *pad) {
+    const size_t k = v_in + (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_a) return;
+    const size_t v = idx[k];
+    if (v >= v_in && v - v_in < n_l) pad[v - v_in] = a[k];
+}
+
+// FK_PROVE_SHARE_AL_SORT=0: A keeps its own sort everywhere (read once per process)
+static bool share_al_sort() {
+    static const bool on = [] { const char *e = getenv("FK_PROVE_SHARE_AL_SORT"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
+int key_a_pad(fk_ctx *ctx, const fk_key *key, const QueryIdx *qi, const fk_key::APad **pad) {
+    *pad = nullptr;
+    if (!share_al_sort() || !key || !qi || !qi->a || !qi->a_fp_valid) return FK_OK;
+    const size_t v_in = key->num_input, n_l = key->l_hi - key->l_lo, n_a = key->n_a;
+    // both slices whole (a lone shard, or a rank whose split leaves them whole), the query is this key's, and there are inputs and an aux part
+    if (key->a_lo != 0 || key->a_hi != key->n_a || key->l_lo != 0 || key->l_hi != key->n_l || key->n_l != key->num_aux || !v_in || !n_l || n_a < v_in || qi->n_a != n_a || !key->d_a || !key->d_l) return FK_OK;
+    // Domains above 2^25 keep A's own sort: the array and its levels come ON TOP of A's own (which stay: another context may be reading them), and
+    // what is left for a proof's scratch at 2^26 has not been measured with them (DESIGN.md section 7 [2a]).
+    if (key->m > ((uint64_t)1 << 25)) return FK_OK;
+    const bool l_merged = key->pre_l.lev != nullptr, a_merged = key->pre_a.lev != nullptr;
+    // Found or built under the key's lock: contexts in other host threads prove from the same key.  Nothing another context may be reading is
+    // changed: a filled slot stays as it is, and a slot being filled is not visible before the lock is released.
+    std::lock_guard<std::mutex> lock(key->a_pad_mu);
+    fk_key::APad *slot = nullptr;
+    for (fk_key::APad &c : key->a_pad) {
+        if (c.used && c.fp == qi->a_fp && c.n_a == n_a && c.n_l == n_l) {
+            if (!c.refused && c.d && (c.pre.lev != nullptr) == l_merged) *pad = &c;
+            return FK_OK;
+        }
+        if (!c.used && !slot) slot = &c;
+    }
+    if (!slot) return FK_OK;                 // both slots hold other queries: this one keeps A's own sort
+    fk_key::APad c;
+    c.used = true; c.refused = true; c.fp = qi->a_fp; c.n_a = n_a; c.n_l = n_l;
+    const std::string warnings = ctx->err;   // (precompute_levels appends to it; a refusal here is not the caller's error)
+    auto done = [&](int rc) -> int { *slot = c; ctx->err = rc == FK_OK ? warnings : ctx->err; return rc; };
+    if (a_merged != l_merged) return done(FK_OK);                      // different forms: different window plans, nothing to share
+    const size_t pad_bytes = n_l * sizeof(G1Affine) + 64;
+    if (l_merged) {
+        // the array and its levels must leave free what proofs with this key still allocate, as in key_precompute
+        const MsmPlan p = make_plan(n_l, ctx->window_bits, true);
+        const size_t lev_bytes = (size_t)(p.W - 1) * n_l * sizeof(G1Affine);
+        size_t fr = 0, tot = 0;
+        FK_HIP(ctx, hipMemGetInfo(&fr, &tot));
+        if (pad_bytes + lev_bytes + proof_scratch_still_needed(ctx, key) + ((size_t)2 << 30) > fr) return done(FK_OK);
+    }
+    if (hipMalloc((void **)&c.d, pad_bytes) != hipSuccess) { (void)hipGetLastError(); c.d = nullptr; return done(FK_OK); }
+    hipError_t e = hipMemsetAsync(c.d, 0, pad_bytes, ctx->stream);
+    if (e == hipSuccess && n_a > v_in) {
+        hipLaunchKernelGGL(a_pad_scatter_kernel, dim3((unsigned)((n_a - v_in + 255) / 256)), dim3(256), 0, ctx->stream, key->d_a, qi->a, v_in, n_a, n_l, c.d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(c.d); c.d = nullptr; (void)done(FK_ERR_HIP); FK_HIP(ctx, e); }
+    if (l_merged) {
+        const int rc = precompute_levels<Fq>(ctx, c.d, n_l, &c.pre, "a (padded to l)", false, 0);
+        if (rc != FK_OK || !c.pre.lev || c.pre.W != key->pre_l.W || c.pre.cb != key->pre_l.cb || c.pre.wide != key->pre_l.wide) {
+            if (c.pre.lev) { (void)hipFree(c.pre.lev); c.pre = KeyPre(); }
+            (void)hipFree(c.d); c.d = nullptr;
+            return done(rc);
+        }
+    }
+    c.refused = false;
+    (void)done(FK_OK);
+    *pad = slot;
     return FK_OK;
 }
 

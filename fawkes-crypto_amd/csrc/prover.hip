@@ -11,6 +11,7 @@
 #include <signal.h>
 #include <unistd.h>
 #include "common.hpp"
+#include "../../include/fawkes_hip_inspect.h"
 #include <chrono>
 #include <mutex>
 #include <string.h>
@@ -380,6 +381,20 @@ int fk_key_precomputed(const fk_key *k, uint32_t out[5]) {
     return FK_OK;
 }
 
+int fk_key_a_pad_info(const fk_key *k, uint64_t out[6]) {
+    if (!k || !out) return FK_ERR_BAD_ARG;
+    for (int i = 0; i < 6; i++) out[i] = 0;
+    std::lock_guard<std::mutex> lock(k->a_pad_mu);
+    for (const fk_key::APad &c : k->a_pad) {
+        if (!c.used) continue;
+        out[4]++;
+        if (c.refused || !c.d) { out[3]++; continue; }
+        out[0]++; out[1] = c.n_l; out[2] = c.pre.lev ? c.pre.W : 0;
+        out[5] += (c.n_l + 1) * sizeof(G1Affine) + (c.pre.lev ? (uint64_t)(c.pre.W - 1) * c.pre.n * sizeof(G1Affine) : 0);
+    }
+    return FK_OK;
+}
+
 // per array (h, l, a, b_g1, b_g2): levels held, GiB they occupy (or would: negative when the array has none), and an ESTIMATE of the ms
 // per proof they save -- 4.6e-8 ms per point of G1 work (a G2 point = FK_G2_WORK), the all-levels-vs-none difference measured at 2^25
 // (DESIGN.md section 3.3); 0 for an array too small for levels
@@ -515,7 +530,12 @@ static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const Wi
     lanes_choose(ctx, key);
     FK_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t v_in = key->num_input, v_aux = key->num_aux;
-    for (int i = 0; i < 4; i++) ctx->wit_tail[i] = -1;
+    for (int i = 0; i < 5; i++) ctx->wit_tail[i] = -1;
+    // A adopts L's bucket sort (msm.hip: key_a_pad) where the key's padded A array applies: A = A over the inputs (a small multiplication
+    // of its own) + A over the aux variables in L's index space, which reads L's sort -- no gather, digits or sort of its own.
+    const fk_key::APad *pad = nullptr;
+    FK_TRY(key_a_pad(ctx, key, q.idx, &pad));
+    const bool share_al = pad != nullptr;
     auto body = [&]() -> int {
         // the gathers of the A / B query scalars: on the auxiliary stream -- or, for an early front (the previous proof's tails are
         // still running and HIP maps more streams than there are hardware queues: the auxiliary stream was seen waiting behind the
@@ -525,7 +545,7 @@ static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const Wi
         // B query: inputs and aux variables that occur in some B-side LC;  A query: all inputs, then the aux variables
         // that occur in some A-side LC
         FK_HIP(ctx, ctx->sc_b.reserve(((size_t)v_in + v_aux) * sizeof(Fr)));
-        FK_HIP(ctx, ctx->sc_a.reserve(((size_t)v_in + v_aux) * sizeof(Fr)));
+        if (!share_al) FK_HIP(ctx, ctx->sc_a.reserve(((size_t)v_in + v_aux) * sizeof(Fr)));
         Fr *sb = ctx->sc_b.as<Fr>(), *sa = ctx->sc_a.as<Fr>();
         if (const QueryIdx *qi = q.idx) {
             // resident constraint system: gather this key's slice of each query straight from the index lists
@@ -543,7 +563,7 @@ static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const Wi
                     if (c_hi < hi) FK_TRY(gather_scalars(ctx, d_z, qi->b + c_hi, hi - c_hi, sb + c_hi, ax));
                 }
             }
-            FK_TRY(gather_scalars(ctx, d_z, qi->a + key->a_lo, key->a_hi - key->a_lo, sa + key->a_lo, ax));
+            if (!share_al) FK_TRY(gather_scalars(ctx, d_z, qi->a + key->a_lo, key->a_hi - key->a_lo, sa + key->a_lo, ax));
         } else {
             uint64_t n_b_in = 0, n_b_aux = 0, n_a_aux = 0;
             FK_TRY(compact_scalars(ctx, d_z, q.d_b_in, v_in, sb, &n_b_in, ax));
@@ -560,6 +580,30 @@ static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const Wi
         // B2: the same scalars as B1 when the two slices coincide (B1's sort is reused); its own slice when the key is split by work
         FK_TRY(msm_g2_begin(ctx, key->d_b2, sb + key->b2_lo, key->b2_hi - key->b2_lo, /*reuse_sort=*/key->b2_lo == key->b_lo && key->b2_hi == key->b_hi,
                             &ctx->wit_tail[1], ctx->ev_aux, &key->pre_b2, opt.defer_back));
+        if (share_al) {
+            // A first, on the lane behind the B pair's, and L on the lane A's sort used to have: that lane's hardware queue is free when an early
+            // front begins, while the B pair's and the one next to it still hold the previous proof's G2 tail -- L's sort, the only large one left
+            // besides B's, then runs beside the evaluation instead of behind B's sort (kernel timeline: profiles/share_al_sort_*).
+            // the inputs: z[0, v_in) against a[0, v_in), queued whole (a few thousand points); the aux part goes behind it on the same lane
+            FK_TRY(msm_g1_begin(ctx, key->d_a, d_z, v_in, &ctx->wit_tail[4], z_ready ? z_ready : ctx->ev_aux, nullptr, false, /*uncounted=*/true));
+            const int a_lane = ctx->lane_prev;
+            FK_TRY(msm_g1_begin(ctx, key->d_l, d_z + v_in, key->l_hi - key->l_lo, &ctx->wit_tail[2], z_ready ? z_ready : ctx->ev_aux, &key->pre_l, opt.defer_back));
+            const int l_lane = ctx->lane_prev;
+            bool adopted = false;
+            FK_TRY(msm_g1_begin_adopt(ctx, pad->d, d_z + v_in, key->l_hi - key->l_lo, l_lane, a_lane, &adopted, &ctx->wit_tail[3], &pad->pre, opt.defer_back));
+            if (adopted) return FK_OK;
+            // L's lane cannot lend (an experiment build run with fewer lanes: A's inputs and L shared one): A as before, whole, over its own
+            // gathered scalars; the inputs' sum is collected and dropped
+            G1Xyzz drop;
+            FK_TRY(msm_g1_end(ctx, ctx->wit_tail[4], &drop));
+            ctx->wit_tail[4] = -1;
+            FK_HIP(ctx, ctx->sc_a.reserve(((size_t)v_in + v_aux) * sizeof(Fr)));
+            sa = ctx->sc_a.as<Fr>();
+            FK_TRY(gather_scalars(ctx, d_z, q.idx->a, key->n_a, sa, ax));
+            FK_HIP(ctx, hipEventRecord(ctx->ev_aux, ax));
+            FK_TRY(msm_g1_begin(ctx, key->d_a, sa, key->n_a, &ctx->wit_tail[3], ctx->ev_aux, &key->pre_a, opt.defer_back));
+            return FK_OK;
+        }
         FK_TRY(msm_g1_begin(ctx, key->d_l, d_z + v_in + key->l_lo, key->l_hi - key->l_lo, &ctx->wit_tail[2], z_ready ? z_ready : ctx->ev_aux, &key->pre_l, opt.defer_back));   // L reads z itself: it need not wait for the gathers
         FK_TRY(msm_g1_begin(ctx, key->d_a, sa + key->a_lo, key->a_hi - key->a_lo, &ctx->wit_tail[3], ctx->ev_aux, &key->pre_a, opt.defer_back));
         return FK_OK;
@@ -574,11 +618,11 @@ extern "C++" {
 namespace fk {
 // The witness half of an early front (spmv.hip: early_front): L, A, B1, B2 of the NEXT proof begun with their accumulations and
 // tails deferred, exactly as prove_msms_dev's sorts-first path would begin them.  Returns 0 when the schedule does not apply.
-int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q, int tails_out[4]) {
+int early_witness_begin(fk_ctx *ctx, const fk_key *key, const void *d_z, const WitnessQueries &q, int tails_out[5]) {
     if (!early_front_applies(key)) return 0;
     const int rc = witness_begin(ctx, key, (const Fr *)d_z, q, ctx->ev_z, FrontOpts{/*defer_back=*/true, /*gather_on_main=*/true});
     if (rc != FK_OK) return -rc;
-    memcpy(tails_out, ctx->wit_tail, 4 * sizeof(int));
+    memcpy(tails_out, ctx->wit_tail, 5 * sizeof(int));
     return 1;
 }
 bool early_front_applies(const fk_key *key) {
@@ -588,7 +632,7 @@ bool early_front_applies(const fk_key *key) {
 }  // namespace fk
 }  // extern "C++"
 
-// tails: the four witness multiplications to collect (B1, B2, L, A) when they are no longer the context's current ones -- the
+// tails: the witness multiplications to collect (B1, B2, L, A and, where A adopted L's sort, A's inputs) when they are no longer the context's current ones -- the
 // next proof's may have been begun already (early front); default: the context's
 static int witness_end(fk_ctx *ctx, uint8_t out[FK_MSM_RESULT_BYTES], int tail_h = -1, const int *tails = nullptr) {
     if (!tails) {
@@ -596,13 +640,15 @@ static int witness_end(fk_ctx *ctx, uint8_t out[FK_MSM_RESULT_BYTES], int tail_h
         ctx->wit_active = false;
         tails = ctx->wit_tail;
     }
-    const int tw[4] = {tails[0], tails[1], tails[2], tails[3]};
-    G1Xyzz H = G1Xyzz::inf(), L, A, B1; G2Xyzz B2;
+    const int tw[5] = {tails[0], tails[1], tails[2], tails[3], tails[4]};
+    G1Xyzz H = G1Xyzz::inf(), L, A, A_in, B1; G2Xyzz B2;
     auto body = [&]() -> int {
         FK_TRY(msm_g1_end(ctx, tw[0], &B1));
         FK_TRY(msm_g2_end(ctx, tw[1], &B2));
         FK_TRY(msm_g1_end(ctx, tw[2], &L));
         FK_TRY(msm_g1_end(ctx, tw[3], &A));
+        FK_TRY(msm_g1_end(ctx, tw[4], &A_in));       // (no such part: the identity)
+        A.add(A_in);
         if (tail_h >= 0) FK_TRY(msm_g1_end(ctx, tail_h, &H));
         return FK_OK;
     };
@@ -700,7 +746,7 @@ static int prove_msms_run(fk_ctx *ctx, const fk_key *key, Fr *d_a, Fr *d_b, Fr *
         // waiting (fk_prove_r1cs_wait) -- its witness multiplications become the context's current ones, so this proof's are
         // collected by their handles.
         if (gate && run.before_block) {
-            int mine[4];
+            int mine[5];
             memcpy(mine, ctx->wit_tail, sizeof mine);
             ctx->wit_active = false;
             int rce;

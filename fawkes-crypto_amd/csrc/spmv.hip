@@ -647,6 +647,10 @@ static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1
         if ((ia.size() && hipMemcpy(r->d_idx_a, ia.data(), ia.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
             (ib.size() && hipMemcpy(r->d_idx_b, ib.data(), ib.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
         r->qidx.a = r->d_idx_a; r->qidx.b = r->d_idx_b; r->qidx.n_a = ia.size(); r->qidx.n_b = ib.size();
+        // what a key's padded A array (msm.hip: key_a_pad) is cached under: which aux variables the A query takes
+        const int rcf = query_fingerprint(ctx, r->d_idx_a, ia.size(), &r->qidx.a_fp);
+        if (rcf != FK_OK) return fail(rcf);
+        r->qidx.a_fp_valid = true;
     }
     *out = r;
     return FK_OK;
@@ -1049,7 +1053,7 @@ static int early_front(fk_ctx *ctx, int slot) {
     const size_t mb = key->m * sizeof(Fr);
     if (mb > ctx->stage_a.cap || mb > ctx->stage_b.cap || mb > ctx->stage_c.cap) return FK_OK;       // never grow buffers the current proof may still read: no early front
     FK_HIP(ctx, hipEventRecord(ctx->ev_z, ctx->stream));
-    int tails[4];
+    int tails[5];
     const int wb = early_witness_begin(ctx, key, d_z, r1cs_queries(r), tails);
     if (wb < 0) return -wb;
     if (wb == 0) return FK_OK;     // (the schedule does not apply: nothing was queued but the waits)

@@ -59,19 +59,24 @@ def gather_correction(gcal_dir):
 
 
 def proofs_in_pass(launches, dom, log2n, what):
-    """proofs in a pass, from its own dispatch counts"""
+    """proofs in a pass, from its own dispatch counts: 4 G1 accumulations per proof (H, L, A, B1), or 5 where A adopts L's bucket sort (A's inputs
+    are then a small accumulation of their own); the transforms' dispatches tell which"""
     n_acc = launches[dom]
-    if n_acc % 4:
-        raise SystemExit('%s pass: %d G1-accumulate dispatches is not a multiple of 4 (H, L, A, B1 per proof)' % (what, n_acc))
-    proofs = n_acc // 4
     ntt = sum(v for k, v in launches.items() if k.startswith('ntt_pass_kernel'))
     ppt = (log2n + 8) // 9                       # passes per transform
-    # 6 transforms per proof; the key set-up of the pass (fk_setup*: the Lagrange values are one inverse transform) adds one or two
-    extra = ntt - proofs * 6 * ppt
-    if ntt and (ntt % ppt or extra < 0 or extra > 2 * ppt):
-        raise SystemExit('%s pass: %d ntt_pass_kernel dispatches do not fit %d proofs x 6 transforms x %d passes (+ at most 2 set-up transforms)'
-                         % (what, ntt, proofs, ppt))
-    return proofs
+    why = '%s pass: %d G1-accumulate dispatches is not a multiple of 4 (H, L, A, B1 per proof) nor of 5 (the inputs of A apart)' % (what, n_acc)
+    for per in (4, 5):
+        if n_acc % per:
+            continue
+        proofs = n_acc // per
+        # 6 transforms per proof; the key set-up of the pass (fk_setup*: the Lagrange values are one inverse transform) adds one or two
+        extra = ntt - proofs * 6 * ppt
+        if ntt and (ntt % ppt or extra < 0 or extra > 2 * ppt):
+            why = ('%s pass: %d ntt_pass_kernel dispatches do not fit %d proofs x 6 transforms x %d passes (+ at most 2 set-up transforms)'
+                   % (what, ntt, proofs, ppt))
+            continue
+        return proofs
+    raise SystemExit(why)
 
 
 def traffic(fetch_dir, write_dir, log2n, points, out, proofs=None, workload='synthetic', gcal_dir=None, rows=None):
@@ -95,7 +100,7 @@ def traffic(fetch_dir, write_dir, log2n, points, out, proofs=None, workload='syn
              '--no-cpu-baseline` (2^%d rows).  Counter units: KB (x1024 = bytes), summed over the launches of the whole pass (per_kernel); '
              'dominant_kernel is per proof.' % log2n,
         log2n=log2n, rows=rows, proofs_in_the_pass=proofs,
-        proofs_in_the_pass_is='derived: G1-accumulate dispatches / 4, cross-checked against ntt_pass_kernel dispatches (6 transforms x ceil(log2n / 9) passes per proof)',
+        proofs_in_the_pass_is='derived: G1-accumulate dispatches / 4 (/ 5 where A adopts L\'s sort), cross-checked against ntt_pass_kernel dispatches (6 transforms x ceil(log2n / 9) passes per proof)',
         per_kernel=per,
         dominant_kernel=dict(
             name='msm_accumulate_merged_kernel<Fq>' if merged else 'msm_accumulate_kernel<Fq>', launches_per_proof=fl[dom] // proofs, points_per_proof=points, proofs_in_the_pass=proofs,
