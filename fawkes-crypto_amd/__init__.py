@@ -25,3 +25,5 @@ from . import merkle  # noqa: F401
 from . import sparse_merkle  # noqa: F401
 from .sparse_merkle import SparseMerkleTree  # noqa: F401
 from . import merkle_set  # noqa: F401
+from . import batch  # noqa: F401
+from .batch import prove_batch, prove_batch_dev, prove_given_batch  # noqa: F401

@@ -43,6 +43,10 @@ struct CtxScratch {
     // pipeline they hold the NEXT proof's a, b, c (early front, fk_ctx::early) -- every other entry borrows them through scratch_claim
     DevBuf ntt_s1, ntt_s2, ntt_io, hbuf, sc_a, sc_b, scan_tmp, stage_a, stage_b, stage_c, stage_z, stage_d;
     DevBuf check;     // check.hip: the counters of an R1CS check, then the bitmap and the group flags the caller did not ask for
+    // batch_prove.hip: the scratch of one group of a batch call, its own so that a per-proof call right behind a batch call finds the
+    // staging buffers and the lanes as it left them.  bt_vec: a, b, c, h and the transforms' two intermediates (6 x group x m);
+    // bt_z: the witnesses of fk_prove_batch (host rows); bt_sort: histogram, bucket and segment offsets; bt_io: r, s, the five sums per proof, the proofs
+    DevBuf bt_vec, bt_z, bt_sort, bt_entries, bt_partial, bt_wsum, bt_io, bt_scan;
     DevBuf *begin() { return &misc; }
     DevBuf *end() { return begin() + sizeof(CtxScratch) / sizeof(DevBuf); }
     void release_scratch() { for (DevBuf *b = begin(); b != end(); ++b) b->release(); }

@@ -17,6 +17,7 @@
 // the first/last pass of the neighbouring transform; the whole quotient is 6 transforms (quotient_dev: c is subtracted in
 // coefficient space, bellman does 7) = 6*P passes, each reading and writing every element once (64 B/element/pass).
 #include "common.hpp"
+#include "ntt_domain.hpp"
 
 namespace fk {
 
@@ -29,25 +30,6 @@ static constexpr uint32_t NTT_MAX_THREADS = 1024;
 
 enum { PRE_NONE = 0, PRE_TABLE = 1, PRE_ABC = 2, PRE_AB = 3 };
 enum { POST_NONE = 0, POST_CONST = 1, POST_TABLE = 2, POST_TABLE_SUB = 3 };      // _SUB: v * table - xc[out index]
-
-struct ScaleTable {          // value(i) = lo[i & (2^L - 1)] * hi[i >> L]
-    Fr *lo = nullptr, *hi = nullptr;
-    Fr *full = nullptr;      // the products themselves (the quotient's two post-scale tables, memory permitting): one product per element instead of two
-};
-
-struct NttDomain {
-    uint32_t log_n = 0, L = 0, maxdeg = 0;
-    std::vector<uint32_t> degs;
-    Fr omega, omega_inv, minv, zinv;
-    Fr *tw_lo[2] = {nullptr, nullptr}, *tw_hi[2] = {nullptr, nullptr};   // [0] forward, [1] inverse
-    Fr *pq[2] = {nullptr, nullptr};                                       // omega_Rmax^e, e < Rmax/2
-    ScaleTable t_g, t_ginv_minv, t_g_minv, t_ginv_minv_zinv;
-    // single-level inter-pass twiddles: tw_full[dir][pass][k * r] = w^((k * r) << (log_n - lgp - deg)); one product per
-    // element instead of two (lo * hi, then the element).  nullptr: fall back to the two-level tables.
-    std::vector<Fr *> tw_full[2];
-    std::map<uint64_t, ScaleTable> dist_post;   // distributed quotient: (omega_m^-rank)^k tables, key = log_w << 32 | rank
-    std::vector<void *> allocs;
-};
 
 struct PassArgs {
     const Fr *x, *xb, *xc;
@@ -256,7 +238,7 @@ static int make_scale_table(fk_ctx *ctx, NttDomain *d, const Fr &base, const Fr 
     return FK_OK;
 }
 
-static int get_domain(fk_ctx *ctx, uint32_t log_n, NttDomain **out) {
+int get_domain(fk_ctx *ctx, uint32_t log_n, NttDomain **out) {
     auto it = ctx->domains.find(log_n);
     if (it != ctx->domains.end()) { *out = it->second; return FK_OK; }
     // bellman's EvaluationDomain::from_coeffs rejects exp >= S
