@@ -2,14 +2,14 @@
 // a second grid dimension.  Per group of proofs the number of launches is fixed and the host blocks once, at the download of the proofs.
 //
 //   evaluation   one lane per (row, proof, matrix): CSR walk over the resident system, bellman's input rows included, zero behind the rows
-//   quotient     the six transforms of quotient_dev (ntt.hip); the pass kernel is ntt_pass_kernel's structure (LDS tile, two-stage
-//                radix-4 rounds, fused pre / post operations) with blockIdx.y = proof, the tables are the context's NttDomain
+//   quotient     the per-proof prover's: quotient_rows (ntt.hip) over the group's rows -- ntt_pass_kernel with blockIdx.y = proof, the
+//                tables are the context's NttDomain
 //   five sums    one set of kernels, templated on the coordinate field, over SHARED bases: bucket = (proof, window, |digit|) of the
 //                signed digits of the canonical scalar.  histogram (vector atomics) -> one device scan over all buckets of the group
 //                -> scatter of (base index, sign) by atomic cursor -> accumulation, one lane per SEGMENT of a bucket (a witness is
 //                mostly bits: digit 1 of window 0 holds a third of the points) -> reduction, one wave per (proof, window) -> Horner
 //                fold over the windows and normalisation, one lane per proof
-//   assembly     fk_prove_assemble's arithmetic, one proof per lane; the Borsh bytes are written on the device
+//   assembly     the per-proof prover's: groth16_assemble (curve.hpp), one proof per lane; the Borsh bytes are written on the device
 //
 // The proof bytes depend on (key, witness, r, s) only -- every sum is normalised to affine before it is used -- so bucket order (the
 // scatter is unordered), window width and grouping are free; tests/test_gpu_batch_prove.py compares with the per-proof prover byte by byte.
@@ -24,6 +24,8 @@
 using namespace fk;
 
 namespace fk {
+
+static_assert(FK_BATCH_MAX_GROUP <= 65535, "the proof index is gridDim.y");
 
 // ------------------------------------------------------------------------------------------ where a variable lives
 // ONE function of (layout, proof, variable): every stage that reads z goes through it.
@@ -75,226 +77,6 @@ __global__ __launch_bounds__(256) void batch_pad_kernel(Fr *a, Fr *b, Fr *c, uin
     if (t >= m) return;
     Fr *x = blockIdx.z == 0 ? a : (blockIdx.z == 1 ? b : c);
     x[(uint64_t)blockIdx.y * m + t] = Fr::zero();
-}
-
-// ------------------------------------------------------------------------------------------ transforms
-static constexpr uint32_t BT_TILE_LOG = 10;      // R * C <= 1024 elements = 32 KiB of LDS (ntt.hip: NTT_TILE_LOG)
-enum { BPRE_NONE = 0, BPRE_AB = 1 };
-enum { BPOST_NONE = 0, BPOST_CONST = 1, BPOST_TABLE = 2, BPOST_TABLE_SUB = 3 };      // _SUB: v * table - xc[out index]
-
-struct BatchPassArgs {
-    const Fr *x, *xb, *xc;
-    Fr *y;
-    uint32_t log_n, deg, lgp, logC;
-    const Fr *tw_lo, *tw_hi;
-    const Fr *tw_full;
-    uint32_t L;
-    const Fr *pq;
-    uint32_t pq_shift;
-    int pre_mode;
-    int post_mode;
-    Fr post_const;
-    const Fr *post_lo, *post_hi, *post_full;
-};
-
-static __device__ __forceinline__ FrL bt_ldl(const Fr *p, uint64_t i) { const Fr x = p[i]; FrL r; for (int k = 0; k < 8; k++) r.v[k] = x.v[k]; return r; }
-static __device__ __forceinline__ void bt_put(uint4 *p0, uint4 *p1, uint32_t e, const FrL &v) {
-    p0[e] = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
-    p1[e] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
-}
-static __device__ __forceinline__ FrL bt_get(const uint4 *p0, const uint4 *p1, uint32_t e) {
-    const uint4 a = p0[e], b = p1[e];
-    FrL v; v.v[0] = a.x; v.v[1] = a.y; v.v[2] = a.z; v.v[3] = a.w; v.v[4] = b.x; v.v[5] = b.y; v.v[6] = b.z; v.v[7] = b.w;
-    return v;
-}
-
-// One pass of `proofs` transforms of 2^log_n points: grid (tiles, proofs).  Data arrays (x, xb, xc, y) hold one transform per proof,
-// 2^log_n apart; the tables are shared.  Lazily reduced butterflies, canonical in memory (ntt.hip).
-__global__ __launch_bounds__(1024) void batch_ntt_pass_kernel(BatchPassArgs a) {
-    const uint32_t NT = blockDim.x;
-    extern __shared__ uint4 lds[];
-    const uint32_t R = 1u << a.deg, C = 1u << a.logC, tile = R << a.logC;
-    uint4 *p0 = lds, *p1 = lds + tile;
-    const uint32_t tid = threadIdx.x;
-    const uint64_t t = (uint64_t)1 << (a.log_n - a.deg);        // stride between the R inputs
-    const uint64_t pmask = ((uint64_t)1 << a.lgp) - 1;
-    const uint64_t i_base = (uint64_t)blockIdx.x << a.logC;
-    const uint32_t Lmask = (1u << a.L) - 1;
-    const uint64_t boff = (uint64_t)blockIdx.y << a.log_n;      // this proof's transform
-    const Fr *x = a.x + boff, *xb = a.xb ? a.xb + boff : nullptr, *xc = a.xc ? a.xc + boff : nullptr;
-    Fr *y = a.y + boff;
-
-    // ---- load tile (rows r, columns c), fused pre-op and inter-pass twiddle; two elements per lane and step (dual-chain products)
-    for (uint32_t e0 = tid; e0 < tile; e0 += 2 * NT) {
-        const uint32_t e1 = e0 + NT;
-        const bool has1 = e1 < tile;
-        const uint32_t ee1 = has1 ? e1 : e0;
-        const uint32_t c0 = e0 & (C - 1), r0 = e0 >> a.logC, c1 = ee1 & (C - 1), r1 = ee1 >> a.logC;
-        const uint64_t i0 = i_base + c0, i1 = i_base + c1;
-        const uint64_t idx0 = i0 + (uint64_t)r0 * t, idx1 = i1 + (uint64_t)r1 * t;
-        FrL v0 = bt_ldl(x, idx0), v1 = bt_ldl(x, idx1);
-        if (a.pre_mode == BPRE_AB) FrL::mul2(v0, bt_ldl(xb, idx0), v1, bt_ldl(xb, idx1), v0, v1);
-        if (a.lgp) {
-            const uint64_t y0 = (i0 & pmask) * r0, y1 = (i1 & pmask) * r1;
-            if (a.tw_full) {
-                FrL::mul2(v0, bt_ldl(a.tw_full, y0), v1, bt_ldl(a.tw_full, y1), v0, v1);
-            } else {
-                const uint64_t x0 = y0 << (a.log_n - a.lgp - a.deg), x1 = y1 << (a.log_n - a.lgp - a.deg);
-                FrL w0, w1;
-                FrL::mul2(bt_ldl(a.tw_lo, x0 & Lmask), bt_ldl(a.tw_hi, x0 >> a.L), bt_ldl(a.tw_lo, x1 & Lmask), bt_ldl(a.tw_hi, x1 >> a.L), w0, w1);
-                FrL::mul2(v0, w0, v1, w1, v0, v1);
-            }
-        }
-        bt_put(p0, p1, e0, v0);
-        if (has1) bt_put(p0, p1, e1, v1);
-    }
-    __syncthreads();
-
-    // ---- deg DIF stages in LDS, two at a time (a lane holds the four elements of a radix-4 group in registers)
-    const uint32_t ngrp = tile >> 2;
-    uint32_t rnd = 0;
-    for (; rnd + 1 < a.deg; rnd += 2) {
-        const uint32_t bit = (R >> 1) >> rnd, bq = bit >> 1;
-        for (uint32_t g = tid; g < ngrp; g += NT) {
-            const uint32_t c = g & (C - 1), ii = g >> a.logC;
-            const uint32_t d = ii & (bq - 1);
-            const uint32_t row = ((ii - d) << 2) + d;                 // bits `bit` and `bq` of the row are zero
-            const uint32_t e0 = (row << a.logC) + c, e1 = e0 + (bq << a.logC), e2 = e0 + (bit << a.logC), e3 = e2 + (bq << a.logC);
-            FrL x0 = bt_get(p0, p1, e0), x1 = bt_get(p0, p1, e1), x2 = bt_get(p0, p1, e2), x3 = bt_get(p0, p1, e3);
-            FrL s0, d0, s1, d1, y0, y1;
-            FrL::addsub2(x0, x2, x0, x2, s0, d0);
-            FrL::addsub2(x1, x3, x1, x3, s1, d1);
-            FrL::addsub2(s0, s1, s0, s1, y0, y1);
-            if (bq == 1) {                                            // d = 0: T1 = T3 = 1, T2 = the fourth root
-                d1 = FrL::mul(d1, bt_ldl(a.pq, (1u << rnd) << a.pq_shift));
-            } else {
-                FrL::mul2(d0, bt_ldl(a.pq, (d << rnd) << a.pq_shift), d1, bt_ldl(a.pq, ((d + bq) << rnd) << a.pq_shift), d0, d1);
-            }
-            FrL y2, y3;
-            FrL::addsub2(d0, d1, d0, d1, y2, y3);
-            if (bq != 1) {
-                const FrL t3 = bt_ldl(a.pq, (d << (rnd + 1)) << a.pq_shift);
-                FrL::mul2(y1, t3, y3, t3, y1, y3);
-            }
-            bt_put(p0, p1, e0, y0);
-            bt_put(p0, p1, e1, y1);
-            bt_put(p0, p1, e2, y2);
-            bt_put(p0, p1, e3, y3);
-        }
-        __syncthreads();
-    }
-    if (rnd < a.deg) {                        // odd degree: the last stage stands alone, and all its twiddles are 1
-        const uint32_t nbf = tile >> 1;
-        for (uint32_t bf = tid; bf < nbf; bf += NT) {
-            const uint32_t c = bf & (C - 1), ii = bf >> a.logC;
-            const uint32_t e0 = ((ii << 1) << a.logC) + c, e1 = e0 + C;
-            FrL u = bt_get(p0, p1, e0), w = bt_get(p0, p1, e1), sm, df;
-            FrL::addsub2(u, w, u, w, sm, df);
-            bt_put(p0, p1, e0, sm);
-            bt_put(p0, p1, e1, df);
-        }
-        __syncthreads();
-    }
-
-    // ---- store tile to its autosorted place, fused post-op
-    for (uint32_t e0 = tid; e0 < tile; e0 += 2 * NT) {
-        const uint32_t e1_ = e0 + NT;
-        const bool has1 = e1_ < tile;
-        const uint32_t e1 = has1 ? e1_ : e0;
-        uint32_t c0, rr0, c1, rr1;
-        if (a.lgp == 0) { rr0 = e0 & (R - 1); c0 = e0 >> a.deg; rr1 = e1 & (R - 1); c1 = e1 >> a.deg; }      // first pass: runs of R outputs
-        else { c0 = e0 & (C - 1); rr0 = e0 >> a.logC; c1 = e1 & (C - 1); rr1 = e1 >> a.logC; }            // later passes: runs of C outputs
-        const uint32_t q0 = a.deg ? (__brev(rr0) >> (32 - a.deg)) : 0, q1 = a.deg ? (__brev(rr1) >> (32 - a.deg)) : 0;
-        FrL v0 = bt_get(p0, p1, (q0 << a.logC) + c0), v1 = bt_get(p0, p1, (q1 << a.logC) + c1);
-        const uint64_t i0 = i_base + c0, i1 = i_base + c1;
-        const uint64_t k0 = i0 & pmask, k1 = i1 & pmask;
-        const uint64_t o0 = ((i0 - k0) << a.deg) + k0 + ((uint64_t)rr0 << a.lgp), o1 = ((i1 - k1) << a.deg) + k1 + ((uint64_t)rr1 << a.lgp);
-        if (a.post_mode == BPOST_CONST) {
-            FrL pc; for (int k = 0; k < 8; k++) pc.v[k] = a.post_const.v[k];
-            FrL::mul2(v0, pc, v1, pc, v0, v1);
-        } else if (a.post_mode == BPOST_TABLE || a.post_mode == BPOST_TABLE_SUB) {
-            if (a.post_full) FrL::mul2(v0, bt_ldl(a.post_full, o0), v1, bt_ldl(a.post_full, o1), v0, v1);
-            else {
-                FrL s0, s1;
-                FrL::mul2(bt_ldl(a.post_lo, o0 & Lmask), bt_ldl(a.post_hi, o0 >> a.L), bt_ldl(a.post_lo, o1 & Lmask), bt_ldl(a.post_hi, o1 >> a.L), s0, s1);
-                FrL::mul2(v0, s0, v1, s1, v0, v1);
-            }
-            if (a.post_mode == BPOST_TABLE_SUB) FrL::sub2(v0, bt_ldl(xc, o0), v1, bt_ldl(xc, o1), v0, v1);
-        }
-        y[o0] = canon(v0);
-        if (has1) y[o1] = canon(v1);
-    }
-}
-
-struct BatchNttOp {
-    bool inverse = false;
-    int pre_mode = BPRE_NONE; const Fr *xb = nullptr, *xc = nullptr;
-    int post_mode = BPOST_NONE; Fr post_const; const ScaleTable *post = nullptr;
-};
-
-// All passes of `proofs` transforms: in -> ... -> final_dst, intermediates alternate between tmp1 and tmp2 (ntt.hip: ntt_exec's rules:
-// tmp1 != tmp2, neither aliases in / xb / xc / final_dst; final_dst may alias `in` only when there are >= 2 passes).
-static int batch_ntt_exec(fk_ctx *ctx, NttDomain *d, const BatchNttOp &op, const Fr *in, Fr *tmp1, Fr *tmp2, Fr *final_dst, uint32_t proofs) {
-    const uint32_t P = (uint32_t)d->degs.size();
-    const int dir = op.inverse ? 1 : 0;
-    const Fr *src = in;
-    uint32_t lgp = 0;
-    for (uint32_t i = 0; i < P; i++) {
-        const uint32_t deg = d->degs[i];
-        Fr *dst = i == P - 1 ? final_dst : ((((P - 2 - i) & 1) == 0) ? tmp1 : tmp2);
-        BatchPassArgs a{};
-        a.x = src; a.xb = op.xb; a.xc = op.xc; a.y = dst;
-        a.log_n = d->log_n; a.deg = deg; a.lgp = lgp;
-        uint32_t logC = 3;
-        if (logC > BT_TILE_LOG - deg) logC = BT_TILE_LOG - deg;
-        if (logC > d->log_n - deg) logC = d->log_n - deg;
-        a.logC = logC;
-        a.tw_lo = d->tw_lo[dir]; a.tw_hi = d->tw_hi[dir]; a.L = d->L;
-        a.tw_full = d->tw_full[dir].empty() ? nullptr : d->tw_full[dir][i];
-        a.pq = d->pq[dir]; a.pq_shift = d->maxdeg - deg;
-        a.pre_mode = i == 0 ? op.pre_mode : BPRE_NONE;
-        a.post_mode = i == P - 1 ? op.post_mode : BPOST_NONE;
-        a.post_const = op.post_const;
-        if (op.post) { a.post_lo = op.post->lo; a.post_hi = op.post->hi; a.post_full = op.post->full; }
-        const uint64_t nblk = ((uint64_t)1 << (d->log_n - deg)) >> logC;
-        const size_t lds_bytes = (size_t)2 * sizeof(uint4) << (deg + logC);
-        uint32_t threads = 1u << (deg + logC > 1 ? deg + logC - 2 : 0);      // one lane per two butterflies
-        if (threads < 64) threads = 64;
-        if (threads > 512) threads = 512;
-        hipLaunchKernelGGL(batch_ntt_pass_kernel, dim3((unsigned)nblk, proofs), dim3(threads), lds_bytes, ctx->stream, a);
-        FK_HIP(ctx, hipGetLastError());
-        src = dst;
-        lgp += deg;
-    }
-    return FK_OK;
-}
-
-// quotient_dev (ntt.hip) for `proofs` rows of m = 2^log_m elements each: six transforms, c subtracted in coefficient space.
-// a, b, c are zero behind their rows already; s1, s2: proofs x m scratch.
-static int batch_quotient(fk_ctx *ctx, Fr *d_a, Fr *d_b, Fr *d_c, uint32_t log_m, uint32_t proofs, Fr *s1, Fr *s2, Fr *d_h) {
-    NttDomain *d = nullptr;
-    FK_TRY(get_domain(ctx, log_m, &d));
-    const size_t bytes = ((size_t)proofs * sizeof(Fr)) << log_m;
-    const bool multi = d->degs.size() >= 2;
-    {   // c: ifft only, with 1 / (m Z(g)) on the way out
-        BatchNttOp invc; invc.inverse = true; invc.post_mode = BPOST_CONST; invc.post_const = Fr::mul(d->minv, d->zinv);
-        if (multi) FK_TRY(batch_ntt_exec(ctx, d, invc, d_c, s1, s2, d_c, proofs));
-        else { FK_TRY(batch_ntt_exec(ctx, d, invc, d_c, s1, s2, s1, proofs)); FK_HIP(ctx, hipMemcpyAsync(d_c, s1, bytes, hipMemcpyDeviceToDevice, ctx->stream)); }
-    }
-    for (Fr *x : {d_a, d_b}) {
-        BatchNttOp inv; inv.inverse = true; inv.post_mode = BPOST_TABLE; inv.post = &d->t_g_minv;      // ifft, then * g^i / m
-        BatchNttOp fwd;
-        if (multi) {
-            FK_TRY(batch_ntt_exec(ctx, d, inv, x, s1, s2, x, proofs));
-            FK_TRY(batch_ntt_exec(ctx, d, fwd, x, s1, s2, x, proofs));
-        } else {
-            FK_TRY(batch_ntt_exec(ctx, d, inv, x, s1, s2, s1, proofs));
-            FK_TRY(batch_ntt_exec(ctx, d, fwd, s1, s2, s2, x, proofs));
-        }
-    }
-    BatchNttOp fin; fin.inverse = true; fin.pre_mode = BPRE_AB; fin.xb = d_b; fin.xc = d_c;
-    fin.post_mode = BPOST_TABLE_SUB; fin.post = &d->t_ginv_minv_zinv;
-    return batch_ntt_exec(ctx, d, fin, d_a, s1, s2, d_h, proofs);
 }
 
 // ------------------------------------------------------------------------------------------ multiplications over shared bases
@@ -402,8 +184,7 @@ __global__ __launch_bounds__(64) void batch_horner_kernel(const Xyzz<F> *wsum, u
 }
 
 // ------------------------------------------------------------------------------------------ assembly
-struct AssembleKey { G1Affine alpha_g1, beta_g1, delta_g1; G2Affine beta_g2, delta_g2; };
-// fk_prove_assemble (prover.hip) for one part per proof: parts = proofs x FK_MSM_RESULT_BYTES (H, L, A, B1, B2 raw affine)
+// groth16_assemble (curve.hpp) for one part per proof: parts = proofs x FK_MSM_RESULT_BYTES (H, L, A, B1, B2 raw affine); the Borsh bytes are written here
 __global__ __launch_bounds__(64) void batch_assemble_kernel(AssembleKey key, const uint8_t *parts, const Fr *r, const Fr *s, uint32_t proofs, uint8_t *out) {
     const uint32_t p = blockIdx.x * 64 + threadIdx.x;
     if (p >= proofs) return;
@@ -411,25 +192,7 @@ __global__ __launch_bounds__(64) void batch_assemble_kernel(AssembleKey key, con
     const G1Xyzz H = G1Xyzz::from_affine(*(const G1Affine *)q), L = G1Xyzz::from_affine(*(const G1Affine *)(q + 64));
     const G1Xyzz A = G1Xyzz::from_affine(*(const G1Affine *)(q + 128)), B1 = G1Xyzz::from_affine(*(const G1Affine *)(q + 192));
     const G2Xyzz B2 = G2Xyzz::from_affine(*(const G2Affine *)(q + 256));
-    const Fr rm = r[p], sm = s[p];
-    const Fr rc = Fr::from_mont(rm), sc = Fr::from_mont(sm), rsc = Fr::from_mont(Fr::mul(rm, sm));
-    const G1Xyzz d1 = G1Xyzz::from_affine(key.delta_g1), a1 = G1Xyzz::from_affine(key.alpha_g1), b1 = G1Xyzz::from_affine(key.beta_g1);
-    const G2Xyzz d2 = G2Xyzz::from_affine(key.delta_g2);
-    G1Xyzz gA = G1Xyzz::mul_scalar(d1, rc.v); gA.add_mixed(key.alpha_g1); gA.add(A);
-    G2Xyzz gB = G2Xyzz::mul_scalar(d2, sc.v); gB.add_mixed(key.beta_g2); gB.add(B2);
-    G1Xyzz gC = G1Xyzz::mul_scalar(d1, rsc.v);
-    gC.add(G1Xyzz::mul_scalar(a1, sc.v));
-    gC.add(G1Xyzz::mul_scalar(b1, rc.v));
-    gC.add(G1Xyzz::mul_scalar(A, sc.v));
-    gC.add(G1Xyzz::mul_scalar(B1, rc.v));
-    gC.add(H); gC.add(L);
-    const G1Affine pa = gA.to_affine(), pc = gC.to_affine();
-    const G2Affine pb = gB.to_affine();
-    // fawkes Borsh: canonical LE coordinates, infinity = zeros
-    Fq *o = (Fq *)(out + (size_t)p * FK_PROOF_BYTES);
-    o[0] = Fq::from_mont(pa.x); o[1] = Fq::from_mont(pa.y);
-    o[2] = Fq::from_mont(pb.x.c0); o[3] = Fq::from_mont(pb.x.c1); o[4] = Fq::from_mont(pb.y.c0); o[5] = Fq::from_mont(pb.y.c1);
-    o[6] = Fq::from_mont(pc.x); o[7] = Fq::from_mont(pc.y);
+    groth16_assemble(key, H, L, A, B1, B2, r[p], s[p], (Fq *)(out + (size_t)p * FK_PROOF_BYTES));
 }
 
 // ------------------------------------------------------------------------------------------ plan (host)
@@ -627,10 +390,9 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
         FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: domain %llu > 2^%d: one proof fills the device, use fk_prove_r1cs_dev", who, (unsigned long long)key->m, FK_BATCH_MAX_LOG_M);
     uint64_t rows = 0;
     FK_TRY(r1cs_fits_key(ctx, r, key, &rows));
-    if (r->qidx.n_b != key->n_b) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: b query needs %llu points, key holds %llu", (unsigned long long)r->qidx.n_b, (unsigned long long)key->n_b);
-    if (r->qidx.n_a != key->n_a) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: a query needs %llu points, key holds %llu", (unsigned long long)r->qidx.n_a, (unsigned long long)key->n_a);
-    if (key->n_l != key->num_aux || key->n_h + 1 != key->m) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: key arrays do not match its domain and variable counts");
-    if (key->delta_g1.is_inf() || key->delta_g2.is_inf()) FK_SET_ERR(ctx, FK_ERR_UNEXPECTED_IDENTITY, "delta is the identity");
+    FK_TRY(queries_fit_key(ctx, &r->qidx, key));
+    FK_TRY(key_arrays_whole(ctx, key));
+    FK_TRY(key_delta_ok(ctx, key));
     FK_TRY(bt_claim(ctx, who));
     const auto t_begin = std::chrono::steady_clock::now();
     fk_batch_opts eff;
@@ -640,6 +402,8 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
     const uint64_t m = key->m;
     const uint32_t log_m = ceil_log2_u64(m), G = plan.group, nvars = key->num_input + key->num_aux;
     const uint64_t nmax = std::max(std::max(m - 1, key->n_l), std::max(key->n_a, key->n_b));
+    NttDomain *dom = nullptr;
+    FK_TRY(get_domain(ctx, log_m, &dom));
     BtEvents evs;
     if (tm) FK_TRY(evs.init(ctx));
     // scratch of one group
@@ -650,7 +414,7 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
     const size_t io_r = 0, io_s = up256((size_t)G * sizeof(Fr)), io_parts = 2 * io_s, io_out = io_parts + up256((size_t)G * FK_MSM_RESULT_BYTES);
     FK_HIP(ctx, ctx->bt_io.reserve(io_out + (size_t)G * FK_PROOF_BYTES));
     uint8_t *io = ctx->bt_io.as<uint8_t>();
-    AssembleKey ak{key->alpha_g1, key->beta_g1, key->delta_g1, key->beta_g2, key->delta_g2};
+    const AssembleKey ak = key->assemble_key();
     BatchEvalArgs ea;
     for (int k = 0; k < 3; k++) { ea.ptr[k] = r->ptr[k]; ea.col[k] = r->col[k]; ea.cidx[k] = r->cidx[k]; }
     ea.out[0] = va; ea.out[1] = vb; ea.out[2] = vc;
@@ -664,7 +428,7 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
         hipLaunchKernelGGL(batch_eval_kernel, dim3((unsigned)((m + 255) / 256), g, 3), dim3(256), 0, ctx->stream, ea, (const Fr *)r->table, zv, r->num_gates, rows, m);
         FK_HIP(ctx, hipGetLastError());
         FK_TRY(evs.mark(ctx, 1));
-        FK_TRY(batch_quotient(ctx, va, vb, vc, log_m, g, s1, s2, vh));
+        FK_TRY(quotient_rows(ctx, dom, va, vb, vc, g, s1, s2, vh));
         FK_TRY(evs.mark(ctx, 2));
         uint8_t *parts = io + io_parts;
         auto shape = [&](uint32_t c, uint64_t n) { return bt_msm_shape(n, c, plan.segment, g); };      // the plan's width and segment for the n points of one query
@@ -774,13 +538,15 @@ int fk_batch_quotient_dev(fk_ctx *ctx, void *d_a, void *d_b, void *d_c, uint64_t
     if (n_rows == 0 || n_rows > m) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: %llu rows in a domain of %llu", who, (unsigned long long)n_rows, (unsigned long long)m);
     if (count > FK_BATCH_MAX_GROUP || (uint64_t)count * m >= ((uint64_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: too many proofs for one group", who);
     FK_TRY(bt_claim(ctx, who));
+    NttDomain *dom = nullptr;
+    FK_TRY(get_domain(ctx, log_m, &dom));
     FK_HIP(ctx, ctx->bt_vec.reserve(2 * (size_t)count * m * sizeof(Fr)));
     Fr *s1 = ctx->bt_vec.as<Fr>(), *s2 = s1 + (size_t)count * m;
     if (n_rows < m) {
         hipLaunchKernelGGL(batch_pad_kernel, dim3((unsigned)((m - n_rows + 255) / 256), count, 3), dim3(256), 0, ctx->stream, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c, n_rows, m);
         FK_HIP(ctx, hipGetLastError());
     }
-    FK_TRY(batch_quotient(ctx, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c, log_m, count, s1, s2, (Fr *)d_h));
+    FK_TRY(quotient_rows(ctx, dom, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c, count, s1, s2, (Fr *)d_h));
     FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FK_OK;
 }); }

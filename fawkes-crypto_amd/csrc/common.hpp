@@ -187,6 +187,7 @@ struct fk_key {
     fk::G2Affine *d_b2 = nullptr;
     fk::G1Affine alpha_g1, beta_g1, delta_g1;
     fk::G2Affine beta_g2, delta_g2;
+    fk::AssembleKey assemble_key() const { return {alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2}; }
     fk::KeyPre pre_h, pre_l, pre_a, pre_b1, pre_b2;       // optional (memory permitting), see key_precompute
     // A's aux bases in L's index space (msm.hip: key_a_pad): d[j] = A's base of aux variable j if that variable occurs in the A query, else
     // the point at infinity -- so that A's aux part is a multiplication over L's scalars and adopts L's bucket sort (prover.hip:

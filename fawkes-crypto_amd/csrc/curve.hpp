@@ -123,7 +123,7 @@ struct alignas(16) Xyzz {
         return Affine<F>{F::mul(x, izz), F::mul(y, izzz)};
     }
 
-    // k * p, k canonical 8 x u32 LE (host-side assembly only)
+    // k * p, k canonical 8 x u32 LE (the proof's assembly only: groth16_assemble)
     static FK_HD Xyzz mul_scalar(const Xyzz &p, const uint32_t k[8]) {
         Xyzz acc = inf();
         for (int i = 255; i >= 0; i--) {
@@ -158,5 +158,33 @@ using G1Affine = Affine<Fq>;
 using G2Affine = Affine<Fq2>;
 using G1Xyzz = Xyzz<Fq>;
 using G2Xyzz = Xyzz<Fq2>;
+
+// The key's five points that enter every proof.
+struct AssembleKey { G1Affine alpha_g1, beta_g1, delta_g1; G2Affine beta_g2, delta_g2; };
+
+// The Groth16 proof from the five sums H, L, A_q, B1 (G1) and B2 (G2) and r, s (Montgomery form):
+//   A = alpha + A_q + r*delta1 ; B = beta2 + B2 + s*delta2 ;
+//   C = H + L + s*A_q + r*B1 + s*alpha + r*beta1 + (r s)*delta1   
+// out: fawkes Borsh, A.x A.y B.x.c0 B.x.c1 B.y.c0 B.y.c1 C.x C.y as canonical LE words, infinity = zeros (Fq::from_mont(0) == 0).
+// The one place the proof bytes come from: fk_prove_assemble on the host, batch_assemble_kernel one proof per lane.
+static FK_HD void groth16_assemble(const AssembleKey &key, const G1Xyzz &H, const G1Xyzz &L, const G1Xyzz &A, const G1Xyzz &B1, const G2Xyzz &B2,
+                                   const Fr &rm, const Fr &sm, Fq out[8]) {
+    const Fr rc = Fr::from_mont(rm), sc = Fr::from_mont(sm), rsc = Fr::from_mont(Fr::mul(rm, sm));
+    const G1Xyzz d1 = G1Xyzz::from_affine(key.delta_g1), a1 = G1Xyzz::from_affine(key.alpha_g1), b1 = G1Xyzz::from_affine(key.beta_g1);
+    const G2Xyzz d2 = G2Xyzz::from_affine(key.delta_g2);
+    G1Xyzz gA = G1Xyzz::mul_scalar(d1, rc.v); gA.add_mixed(key.alpha_g1); gA.add(A);
+    G2Xyzz gB = G2Xyzz::mul_scalar(d2, sc.v); gB.add_mixed(key.beta_g2); gB.add(B2);
+    G1Xyzz gC = G1Xyzz::mul_scalar(d1, rsc.v);
+    gC.add(G1Xyzz::mul_scalar(a1, sc.v));
+    gC.add(G1Xyzz::mul_scalar(b1, rc.v));
+    gC.add(G1Xyzz::mul_scalar(A, sc.v));
+    gC.add(G1Xyzz::mul_scalar(B1, rc.v));
+    gC.add(H); gC.add(L);
+    const G1Affine pa = gA.to_affine(), pc = gC.to_affine();
+    const G2Affine pb = gB.to_affine();
+    out[0] = Fq::from_mont(pa.x); out[1] = Fq::from_mont(pa.y);
+    out[2] = Fq::from_mont(pb.x.c0); out[3] = Fq::from_mont(pb.x.c1); out[4] = Fq::from_mont(pb.y.c0); out[5] = Fq::from_mont(pb.y.c1);
+    out[6] = Fq::from_mont(pc.x); out[7] = Fq::from_mont(pc.y);
+}
 
 }  // namespace fk

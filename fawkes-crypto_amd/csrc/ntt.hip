@@ -75,6 +75,12 @@ __global__ __launch_bounds__(NTT_MAX_THREADS) void ntt_pass_kernel(PassArgs a) {
     const uint64_t pmask = ((uint64_t)1 << a.lgp) - 1;
     const uint64_t i_base = (uint64_t)blockIdx.x << a.logC;
     const uint32_t Lmask = (1u << a.L) - 1;
+    // grid (tiles, proofs): the data arrays hold one transform per proof, 2^log_n apart; the tables are shared.  The offset is uniform
+    // (scalar registers); a.xb / a.xc are read only under their pre / post modes.
+    const uint64_t boff = (uint64_t)blockIdx.y << a.log_n;
+    a.x += boff; a.y += boff;
+    if (a.xb) a.xb += boff;
+    if (a.xc) a.xc += boff;
 
     // Every lane handles two elements / butterflies per step (e and e + NTT_THREADS) so that the field products can
     // be issued as dual chains (FL::mul2: two interleaved accumulator chains per wave, the same instruction count).
@@ -342,10 +348,11 @@ struct NttOp {
     int post_mode = POST_NONE; Fr post_const; const ScaleTable *post = nullptr;
 };
 
-// Runs all passes: in -> ... -> final_dst, intermediates alternate between tmp1 and tmp2.
+// Runs all passes of `proofs` transforms (grid (tiles, proofs): every data array holds one transform per proof, 2^log_n apart):
+// in -> ... -> final_dst, intermediates alternate between tmp1 and tmp2.
 // Requirements: tmp1 != tmp2, neither aliases in / xb / xc / final_dst; final_dst may alias `in` only
 // when there are >= 2 passes.
-static int ntt_exec(fk_ctx *ctx, NttDomain *d, const NttOp &op, const Fr *in, Fr *tmp1, Fr *tmp2, Fr *final_dst) {
+static int ntt_exec(fk_ctx *ctx, NttDomain *d, const NttOp &op, const Fr *in, Fr *tmp1, Fr *tmp2, Fr *final_dst, uint32_t proofs) {
     const uint32_t P = (uint32_t)d->degs.size();
     const int dir = op.inverse ? 1 : 0;
     const Fr *src = in;
@@ -375,12 +382,12 @@ static int ntt_exec(fk_ctx *ctx, NttDomain *d, const NttOp &op, const Fr *in, Fr
         const size_t lds_bytes = (size_t)2 * sizeof(uint4) << (deg + logC);
         void (*kern)(PassArgs) = ntt_pass_kernel<FrL>;
         FK_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        FK_TRY(stats_begin(ctx, ctx->ev_ntt, (uint64_t)1 << d->log_n));
+        FK_TRY(stats_begin(ctx, ctx->ev_ntt, (uint64_t)proofs << d->log_n));
         // one lane per two butterflies (the kernel issues the field products of a pair as dual chains)
         uint32_t threads = 1u << (deg + logC > 1 ? deg + logC - 2 : 0);
         if (threads < 64) threads = 64;
         if (threads > ctx->ntt_threads) threads = ctx->ntt_threads;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(threads), lds_bytes, ctx->stream, a);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk, proofs), dim3(threads), lds_bytes, ctx->stream, a);
         FK_HIP(ctx, hipGetLastError());
         FK_TRY(stats_end(ctx, ctx->ev_ntt));
         src = dst;
@@ -401,10 +408,42 @@ int ntt_exec_simple(fk_ctx *ctx, Fr *d_data, uint32_t log_n, bool inverse, bool 
     if (!inverse && coset) { op.pre_mode = PRE_TABLE; op.pre = &d->t_g; }            // coset_fft
     if (inverse && !coset) { op.post_mode = POST_CONST; op.post_const = d->minv; }   // ifft
     if (inverse && coset) { op.post_mode = POST_TABLE; op.post = &d->t_ginv_minv; }  // icoset_fft
-    if (d->degs.size() >= 2) return ntt_exec(ctx, d, op, d_data, ctx->ntt_s1.as<Fr>(), ctx->ntt_s2.as<Fr>(), d_data);
-    FK_TRY(ntt_exec(ctx, d, op, d_data, ctx->ntt_s1.as<Fr>(), ctx->ntt_s2.as<Fr>(), ctx->ntt_s1.as<Fr>()));
+    if (d->degs.size() >= 2) return ntt_exec(ctx, d, op, d_data, ctx->ntt_s1.as<Fr>(), ctx->ntt_s2.as<Fr>(), d_data, 1);
+    FK_TRY(ntt_exec(ctx, d, op, d_data, ctx->ntt_s1.as<Fr>(), ctx->ntt_s2.as<Fr>(), ctx->ntt_s1.as<Fr>(), 1));
     FK_HIP(ctx, hipMemcpyAsync(d_data, ctx->ntt_s1.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return FK_OK;
+}
+
+// The quotients of `proofs` rows of m = 2^d->log_n elements each (a, b, c, h: one row per proof, m apart; a, b, c are zero behind their
+// row evaluations already and are used as scratch; s1, s2: proofs x m scratch each).
+// SIX transforms, not bellman's seven.  bellman: h = icoset_fft((A_c o B_c - C_c) / Z(g)) with X_c = coset_fft(ifft(x)).
+// icoset_fft is linear and undoes coset_fft exactly, so icoset_fft(C_c) is simply ifft(c): c never has to visit the coset,
+//     h_i = [g^-i / (m Z(g))] * ifft(A_c o B_c)_i  -  [1 / Z(g)] * ifft(c)_i
+// -- the same field elements (exact arithmetic: the identity holds for ANY a, b, c, satisfied system or not), one transform less.
+int quotient_rows(fk_ctx *ctx, NttDomain *d, Fr *d_a, Fr *d_b, Fr *d_c, uint32_t proofs, Fr *s1, Fr *s2, Fr *d_h) {
+    const size_t bytes = ((size_t)proofs * sizeof(Fr)) << d->log_n;
+    const bool multi = d->degs.size() >= 2;
+    for (Fr *x : {d_a, d_b}) {
+        // ifft followed by the coset shift g^i (first half of coset_fft), fused: * g^i / m on the way out
+        NttOp inv; inv.inverse = true; inv.post_mode = POST_TABLE; inv.post = &d->t_g_minv;
+        NttOp fwd;  // the transform part of coset_fft
+        if (multi) {
+            FK_TRY(ntt_exec(ctx, d, inv, x, s1, s2, x, proofs));
+            FK_TRY(ntt_exec(ctx, d, fwd, x, s1, s2, x, proofs));
+        } else {
+            FK_TRY(ntt_exec(ctx, d, inv, x, s1, s2, s1, proofs));
+            FK_TRY(ntt_exec(ctx, d, fwd, s1, s2, s2, x, proofs));
+        }
+    }
+    {   // c: ifft only, with 1 / (m Z(g)) on the way out
+        NttOp invc; invc.inverse = true; invc.post_mode = POST_CONST; invc.post_const = Fr::mul(d->minv, d->zinv);
+        if (multi) FK_TRY(ntt_exec(ctx, d, invc, d_c, s1, s2, d_c, proofs));
+        else { FK_TRY(ntt_exec(ctx, d, invc, d_c, s1, s2, s1, proofs)); FK_HIP(ctx, hipMemcpyAsync(d_c, s1, bytes, hipMemcpyDeviceToDevice, ctx->stream)); }
+    }
+    // a*b on the coset (fused into the first pass); g^-i / (m Z(g)) and the subtraction of c's scaled coefficients (fused into the last)
+    NttOp fin; fin.inverse = true; fin.pre_mode = PRE_AB; fin.xb = d_b; fin.xc = d_c;
+    fin.post_mode = POST_TABLE_SUB; fin.post = &d->t_ginv_minv_zinv;
+    return ntt_exec(ctx, d, fin, d_a, s1, s2, d_h, proofs);
 }
 
 // h = (A*B - C)/Z.  d_a, d_b, d_c: device arrays with CAPACITY m = next_pow2(n) elements, the first n
@@ -419,38 +458,8 @@ int quotient_dev(fk_ctx *ctx, Fr *d_a, Fr *d_b, Fr *d_c, uint64_t n, Fr *d_h_out
     const size_t bytes = sizeof(Fr) << log_n;
     FK_HIP(ctx, ctx->ntt_s1.reserve(bytes));
     FK_HIP(ctx, ctx->ntt_s2.reserve(bytes));
-    Fr *s1 = ctx->ntt_s1.as<Fr>(), *s2 = ctx->ntt_s2.as<Fr>();
-    Fr *polys[3] = {d_a, d_b, d_c};
-    const bool multi = d->degs.size() >= 2;
-    // SIX transforms, not bellman's seven.  bellman: h = icoset_fft((A_c o B_c - C_c) / Z(g)) with X_c = coset_fft(ifft(x)).
-    // icoset_fft is linear and undoes coset_fft exactly, so icoset_fft(C_c) is simply ifft(c): c never has to visit the coset,
-    //     h_i = [g^-i / (m Z(g))] * ifft(A_c o B_c)_i  -  [1 / Z(g)] * ifft(c)_i
-    // -- the same field elements (exact arithmetic: the identity holds for ANY a, b, c, satisfied system or not), one transform less.
-    for (int k = 0; k < 3; k++) {
-        Fr *x = polys[k];
-        if (m > n) FK_HIP(ctx, hipMemsetAsync(x + n, 0, (m - n) * sizeof(Fr), ctx->stream));
-        if (k == 2) {       // c: ifft only, with 1 / (m Z(g)) on the way out
-            NttOp invc; invc.inverse = true; invc.post_mode = POST_CONST; invc.post_const = Fr::mul(d->minv, d->zinv);
-            if (multi) FK_TRY(ntt_exec(ctx, d, invc, x, s1, s2, x));
-            else { FK_TRY(ntt_exec(ctx, d, invc, x, s1, s2, s1)); FK_HIP(ctx, hipMemcpyAsync(x, s1, bytes, hipMemcpyDeviceToDevice, ctx->stream)); }
-            break;
-        }
-        // ifft followed by the coset shift g^i (first half of coset_fft), fused: * g^i / m on the way out
-        NttOp inv; inv.inverse = true; inv.post_mode = POST_TABLE; inv.post = &d->t_g_minv;
-        NttOp fwd;  // the transform part of coset_fft
-        if (multi) {
-            FK_TRY(ntt_exec(ctx, d, inv, x, s1, s2, x));
-            FK_TRY(ntt_exec(ctx, d, fwd, x, s1, s2, x));
-        } else {
-            FK_TRY(ntt_exec(ctx, d, inv, x, s1, s2, s1));
-            FK_TRY(ntt_exec(ctx, d, fwd, s1, s2, s2, x));
-        }
-    }
-    // a*b on the coset (fused into the first pass); g^-i / (m Z(g)) and the subtraction of c's scaled coefficients (fused into the last)
-    NttOp fin; fin.inverse = true; fin.pre_mode = PRE_AB; fin.xb = d_b; fin.xc = d_c;
-    fin.post_mode = POST_TABLE_SUB; fin.post = &d->t_ginv_minv_zinv;
-    FK_TRY(ntt_exec(ctx, d, fin, d_a, s1, s2, d_h_out));
-    return FK_OK;
+    if (m > n) for (Fr *x : {d_a, d_b, d_c}) FK_HIP(ctx, hipMemsetAsync(x + n, 0, (m - n) * sizeof(Fr), ctx->stream));
+    return quotient_rows(ctx, d, d_a, d_b, d_c, 1, ctx->ntt_s1.as<Fr>(), ctx->ntt_s2.as<Fr>(), d_h_out);
 }
 
 // ------------------------------------------------------------------------------------------ distributed quotient
@@ -593,8 +602,8 @@ int dq_local(fk_ctx *ctx, Fr *d_x, const Fr *d_xb, const Fr *d_xc, uint32_t log_
         op.post_mode = POST_TABLE; op.post = &it->second;
     }
     Fr *s1 = ctx->ntt_s1.as<Fr>(), *s2 = ctx->ntt_s2.as<Fr>();
-    if (dl->degs.size() >= 2) return ntt_exec(ctx, dl, op, d_x, s1, s2, d_x);
-    FK_TRY(ntt_exec(ctx, dl, op, d_x, s1, s2, s1));
+    if (dl->degs.size() >= 2) return ntt_exec(ctx, dl, op, d_x, s1, s2, d_x, 1);
+    FK_TRY(ntt_exec(ctx, dl, op, d_x, s1, s2, s1, 1));
     FK_HIP(ctx, hipMemcpyAsync(d_x, s1, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return FK_OK;
 }

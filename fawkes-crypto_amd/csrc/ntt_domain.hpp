@@ -1,4 +1,4 @@
-// The evaluation domain of a transform size and its tables (ntt.hip builds and owns them: fk_ctx::domains); shared with batch_prove.hip.
+// The evaluation domain of a transform size and its tables (ntt.hip builds and owns them: fk_ctx::domains), and the quotient over rows of it: what batch_prove.hip takes from ntt.hip.
 #pragma once
 #include "common.hpp"
 
@@ -25,5 +25,7 @@ struct NttDomain {
 
 // ntt.hip: the context's domain of 2^log_n points, built on first use
 int get_domain(fk_ctx *ctx, uint32_t log_n, NttDomain **out);
+// ntt.hip: the quotients of `proofs` rows of 2^d->log_n elements (a, b, c zero behind their rows; s1, s2: proofs << log_n elements of scratch each)
+int quotient_rows(fk_ctx *ctx, NttDomain *d, Fr *d_a, Fr *d_b, Fr *d_c, uint32_t proofs, Fr *s1, Fr *s2, Fr *d_h);
 
 }  // namespace fk

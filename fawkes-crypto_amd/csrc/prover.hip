@@ -11,6 +11,7 @@
 #include <signal.h>
 #include <unistd.h>
 #include "common.hpp"
+#include "r1cs.hpp"
 #include "../../include/fawkes_hip_inspect.h"
 #include <chrono>
 #include <mutex>
@@ -549,10 +550,7 @@ static int witness_begin(fk_ctx *ctx, const fk_key *key, const Fr *d_z, const Wi
         Fr *sb = ctx->sc_b.as<Fr>(), *sa = ctx->sc_a.as<Fr>();
         if (const QueryIdx *qi = q.idx) {
             // resident constraint system: gather this key's slice of each query straight from the index lists
-            if (qi->n_b != key->n_b) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: b query needs %llu points, key holds %llu",
-                                                (unsigned long long)qi->n_b, (unsigned long long)key->n_b);
-            if (qi->n_a != key->n_a) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: a query needs %llu points, key holds %llu",
-                                                (unsigned long long)qi->n_a, (unsigned long long)key->n_a);
+            FK_TRY(queries_fit_key(ctx, qi, key));
             FK_TRY(gather_scalars(ctx, d_z, qi->b + key->b_lo, key->b_hi - key->b_lo, sb + key->b_lo, ax));
             if (key->b2_lo != key->b_lo || key->b2_hi != key->b_hi) {       // key split by work: b_g2's slice is its own (the part b_g1's slice does not cover)
                 const uint64_t lo = key->b2_lo, hi = key->b2_hi;
@@ -876,14 +874,13 @@ int fk_prove_msms_dev(fk_ctx *ctx, const fk_key *key, void *d_a, void *d_b, void
                           ProveRun{{(const uint8_t *)d_a_aux, (const uint8_t *)d_b_in, (const uint8_t *)d_b_aux}}, out, tm);
 }); }
 
-// A = alpha + A_q + r*delta1 ; B = beta2 + B2 + s*delta2 ;
-// C = H + L + s*A_q + r*B1 + s*alpha + r*beta1 + (r s)*delta1   
+// The proof from the partial sums of n_parts ranks or shards (curve.hpp: groth16_assemble)
 int fk_prove_assemble(fk_ctx *ctx, const fk_key *key, const uint8_t *parts, uint32_t n_parts, const uint64_t r_[4],
                       const uint64_t s_[4], uint8_t out[FK_PROOF_BYTES]) { return fk_guard(ctx, [&]() -> int {
     fk_ctx local;                  // host-only routine: usable without a GPU context
     if (!ctx) ctx = &local;
     if (!key || !parts || !n_parts || !r_ || !s_ || !out) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "assemble: null argument");
-    if (key->delta_g1.is_inf() || key->delta_g2.is_inf()) FK_SET_ERR(ctx, FK_ERR_UNEXPECTED_IDENTITY, "delta is the identity");
+    FK_TRY(key_delta_ok(ctx, key));
     G1Xyzz H = G1Xyzz::inf(), L = G1Xyzz::inf(), A = G1Xyzz::inf(), B1 = G1Xyzz::inf();
     G2Xyzz B2 = G2Xyzz::inf();
     for (uint32_t i = 0; i < n_parts; i++) {
@@ -892,22 +889,8 @@ int fk_prove_assemble(fk_ctx *ctx, const fk_key *key, const uint8_t *parts, uint
         B1.add_mixed(g1_from_raw(p + 192)); B2.add_mixed(g2_from_raw(p + 256));
     }
     Fr rm, sm; memcpy(&rm, r_, 32); memcpy(&sm, s_, 32);
-    const Fr rc = Fr::from_mont(rm), sc = Fr::from_mont(sm), rsc = Fr::from_mont(Fr::mul(rm, sm));
-    const G1Xyzz d1 = G1Xyzz::from_affine(key->delta_g1), a1 = G1Xyzz::from_affine(key->alpha_g1), b1 = G1Xyzz::from_affine(key->beta_g1);
-    const G2Xyzz d2 = G2Xyzz::from_affine(key->delta_g2);
-    G1Xyzz gA = G1Xyzz::mul_scalar(d1, rc.v); gA.add_mixed(key->alpha_g1); gA.add(A);
-    G2Xyzz gB = G2Xyzz::mul_scalar(d2, sc.v); gB.add_mixed(key->beta_g2); gB.add(B2);
-    G1Xyzz gC = G1Xyzz::mul_scalar(d1, rsc.v);
-    gC.add(G1Xyzz::mul_scalar(a1, sc.v));
-    gC.add(G1Xyzz::mul_scalar(b1, rc.v));
-    gC.add(G1Xyzz::mul_scalar(A, sc.v));
-    gC.add(G1Xyzz::mul_scalar(B1, rc.v));
-    gC.add(H); gC.add(L);
-    const G1Affine pa = gA.to_affine(), pc = gC.to_affine();
-    const G2Affine pb = gB.to_affine();
-    // fawkes Borsh: canonical LE coordinates, infinity = zeros (Fq::from_mont(0) == 0)
-    const Fq words[8] = {Fq::from_mont(pa.x), Fq::from_mont(pa.y), Fq::from_mont(pb.x.c0), Fq::from_mont(pb.x.c1),
-                         Fq::from_mont(pb.y.c0), Fq::from_mont(pb.y.c1), Fq::from_mont(pc.x), Fq::from_mont(pc.y)};
+    Fq words[8];
+    groth16_assemble(key->assemble_key(), H, L, A, B1, B2, rm, sm, words);
     memcpy(out, words, 256);
     return FK_OK;
 }); }

@@ -88,6 +88,23 @@ static inline int r1cs_fits_key(fk_ctx *ctx, const fk_r1cs_dev *r, const fk_key 
                                                                        (unsigned long long)*rows, (unsigned long long)key->m);
     return FK_OK;
 }
+// The key refusals that the per-proof and the batch prover share (the tests compare codes and texts).
+// A resident system's A / B query sizes against the key's arrays:
+static inline int queries_fit_key(fk_ctx *ctx, const QueryIdx *qi, const fk_key *key) {
+    if (qi->n_b != key->n_b) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: b query needs %llu points, key holds %llu", (unsigned long long)qi->n_b, (unsigned long long)key->n_b);
+    if (qi->n_a != key->n_a) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: a query needs %llu points, key holds %llu", (unsigned long long)qi->n_a, (unsigned long long)key->n_a);
+    return FK_OK;
+}
+// the key's l and h arrays against its own domain and variable counts (the batch prover reads l by variable and h by row)
+static inline int key_arrays_whole(fk_ctx *ctx, const fk_key *key) {
+    if (key->n_l != key->num_aux || key->n_h + 1 != key->m) FK_SET_ERR(ctx, FK_ERR_KEY_MISMATCH, "prove: key arrays do not match its domain and variable counts");
+    return FK_OK;
+}
+// bellman's UnexpectedIdentity: no proof under a key whose delta is the point at infinity
+static inline int key_delta_ok(fk_ctx *ctx, const fk_key *key) {
+    if (key->delta_g1.is_inf() || key->delta_g2.is_inf()) FK_SET_ERR(ctx, FK_ERR_UNEXPECTED_IDENTITY, "delta is the identity");
+    return FK_OK;
+}
 // spmv.hip
 int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a, void *d_b, void *d_c, bool sliced, uint32_t rank, uint32_t log_w, uint64_t n_out, int window);
 int prove_r1cs_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],

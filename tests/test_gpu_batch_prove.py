@@ -146,14 +146,16 @@ def test_batch_msm_every_layout_index_and_width_on_degenerate_bases_and_the_orac
 @pytest.mark.parametrize('count', [1, 3])
 @pytest.mark.parametrize('full', [True, False])
 @pytest.mark.parametrize('log_m', [1, 2, 9, 10, 11, 13])
-def test_batch_quotient_equals_the_single_quotient(ctx, log_m, full, count):
-    """below, at and above one LDS tile (2^10 elements) and two passes (2^11, 2^13); rows = m and m / 2 + 1"""
+def test_batch_quotient_equals_the_single_quotient(ctx, oracle, log_m, full, count):
+    """below, at and above one LDS tile (2^10 elements) and two passes (2^11, 2^13); rows = m and m / 2 + 1.  Both quotients run the same
+    pass kernel (blockIdx.y = proof), so every row is also held to the oracle, which decides"""
     m = 1 << log_m
     rows = m if full else m // 2 + 1
     with Dev(ctx) as d:
         src = [d.alloc(count * m * 32) for _ in range(3)]
         for k, p in enumerate(src):
             ctx.gen_scalars_dev(p, count * m, 77 * log_m + 3 * k + count, 0)        # behind the rows: garbage the entry has to clear
+        host = [ctx.download(p, count * m * 32, np.uint64).reshape(count, m, 4) for p in src]        # the entry uses a, b, c as scratch
         want = []
         one = [d.alloc(m * 32) for _ in range(4)]
         for i in range(count):
@@ -166,6 +168,7 @@ def test_batch_quotient_equals_the_single_quotient(ctx, log_m, full, count):
         got = ctx.download(d_h, count * m * 32).reshape(count, m * 32)
         for i in range(count):
             assert got[i, :(m - 1) * 32].tobytes() == want[i], (log_m, rows, count, i)
+            assert got[i, :(m - 1) * 32].tobytes() == oracle.quotient_h(*(h[i, :rows] for h in host)).tobytes(), (log_m, rows, count, i)
 
 
 # ---------------------------------------------------------------- evaluation
