@@ -7,36 +7,25 @@
 // value zero[l].  The root is one Fr of its own.  Entries are never removed, so a probe that meets an empty slot has seen every slot its
 // key could be in, and an insertion is one compare-and-swap on a key slot: no lane ever waits for another.
 //
-// Update of k ordered writes: merkle_update.hip's scheme -- who the previous toucher of a write's sibling is depends on the indices
-// alone, so the index check, the one stable sort by (index, position) and the per-level plan kernel are that file's (merkle_plan.hpp).
-// Per level, here:
-//   hash        one write per lane, by j: sib = the previous toucher's current value, else the STORED sibling (a bounded probe of the
-//               level's table), else zero[l]; next[j] = H(cur[j], sib) or H(sib, cur[j]); sib goes to siblings[j * depth + l]
-//   write-back  the last write of each run inserts or overwrites (node, value) -- a launch of its own BEHIND the hash launch of its
-//               level, the dense path's hazard: a write whose sibling has no earlier toucher must read the stored value.  Run-last
-//               lanes carry distinct keys: atomicCAS claims a key slot (atomicAdd on the level's counter when it was empty), the value
-//               is then stored plainly
-// The old leaf of a write is the new leaf of the previous element of its level-0 run, else the stored leaf, else 0.
+// Update of k ordered writes and set of k writes (the final state of the update, the new root and nothing else): merkle_plan.hpp's two
+// drivers with this file's store of a level (SmtStore).  get is a bounded probe of the level's table that falls back to zero[l]; put
+// claims the key's slot -- atomicCAS on a key slot, atomicAdd on the level's counter when it was empty -- and then stores the value
+// plainly: the keys of one write-back launch are distinct.  In both drivers the write-back is a launch of its own beside the level's hash
+// launch (behind it in the update, whose hash launch must read the stored sibling; in front of it in the set), so no probe ever runs
+// beside a claim.  For the set the fused form would be sound -- a node is either in the list or read as an absent child, so a probe
+// never looks for a key that a claim of the same launch inserts, and a claimed slot it walks over holds another key whenever it is read
+// -- but it would save one latency-shaped launch per level and put the claim's registers into the hash kernel; the separate launch
+// needs no argument at all.
 //
 // Capacity is settled BEFORE the first launch that writes: a call adds at most min(k, 2^(depth - l)) entries to level l; where the
 // count's upper bound plus that exceeds cap / 2 a larger table is allocated (all of them first: a failure is FK_ERR_OOM with the tree as
 // it was) and the old one rehashed into it, one lane per old slot, out of place.  The exact counts and the error word come to the host
-// by ONE small download queued at the end of each update into pinned memory behind an event; the next call takes them when they have
-// arrived and waits for them only if its upper bounds would otherwise force a growth.  Nothing is downloaded between levels.
+// by ONE small download queued at the end of each update or set into pinned memory behind an event; the next call takes them when they
+// have arrived and waits for them only if its upper bounds would otherwise force a growth.  Nothing is downloaded between levels.
 // Every probe loop is bounded by the capacity; one that runs out (by construction none does) sets the error word and stops its lane.
-//
-// Set of k writes (include/fawkes_hip_merkle_set.h: the final state of the update, the new root and nothing else): merkle_plan.hpp's
-// bulk write with this file's store of a level -- put claims the key's slot as the update's write-back does and stores the value
-// plainly (the keys of a launch are distinct), get is a bounded probe that falls back to zero[l].  The write-back of a level stays a
-// launch of its own, in front of the level's hash launch.  The fused form would be sound -- a node is either in the list or read as an
-// absent child, so a probe never looks for a key that a claim of the same launch inserts, and a claimed slot it walks over holds another
-// key whenever it is read -- but it would save one latency-shaped launch per level and put the claim's registers into the hash kernel;
-// the separate launch needs no argument at all.  Capacity, bounds, the counts' download and the error word are the update's: the same
-// smt_settle_capacity before the first writing launch, the same bound, the same smt_queue_counts behind the last.
 #include "merkle_plan.hpp"
 #include "../../include/fawkes_hip_sparse_merkle.h"
 #include "../../include/fawkes_hip_merkle_set.h"
-#include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
 
 struct fk_smt {
@@ -117,65 +106,18 @@ __global__ __launch_bounds__(POS_THREADS) void smt_rehash_kernel(const uint64_t 
     if (to != SMT_NOT_FOUND) vals[to] = old_vals[s];
 }
 
-// level 0 only: what each write replaces.  keys / ord: the level-0 order
-__global__ __launch_bounds__(POS_THREADS) void smt_old_leaves_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ord, uint32_t k,
-                                                                      const uint64_t *__restrict__ tkeys, const Fr *__restrict__ tvals, uint32_t log_cap,
-                                                                      const Fr *__restrict__ new_leaves, Fr *__restrict__ old, unsigned long long *err) {
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= k) return;
-    const uint64_t node = keys[q];
-    Fr v;
-    if (q > 0 && keys[q - 1] == node) v = new_leaves[ord[q - 1]];
-    else {
-        const uint64_t s = smt_find(tkeys, log_cap, node, err);
-        v = s != SMT_NOT_FOUND ? tvals[s] : Fr::zero();
+// a level as merkle_plan.hpp's drivers see it
+struct SmtStore {
+    uint64_t *keys; Fr *vals; uint32_t log_cap; const Fr *zero_l; unsigned long long *count, *err;
+    __device__ __forceinline__ void put(uint64_t key, const Fr &v) const {
+        const uint64_t s = smt_claim(keys, log_cap, key, count, err);
+        if (s != SMT_NOT_FOUND) vals[s] = v;
     }
-    old[ord[q]] = v;
-}
-
-// depth 0: the tree is its root, the one leaf
-__global__ __launch_bounds__(POS_THREADS) void smt_depth0_old_kernel(const Fr *__restrict__ root, const Fr *__restrict__ new_leaves, uint32_t k, Fr *__restrict__ old) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < k) old[j] = j ? new_leaves[j - 1] : *root;
-}
-
-// tkeys / tvals: the table of level l; zero_l: the default of level l; cur: the writes' values at level l (by j); sib_out: siblings + l, or null
-__global__ __launch_bounds__(POS_THREADS) void smt_hash_kernel(const Fr *__restrict__ tab, uint32_t f, uint32_t p, const uint64_t *__restrict__ tkeys,
-                                                                const Fr *__restrict__ tvals, uint32_t log_cap, const Fr *__restrict__ zero_l,
-                                                                const uint64_t *__restrict__ idx, uint32_t l, uint32_t depth, const uint32_t *__restrict__ prev,
-                                                                const Fr *__restrict__ cur, uint32_t k, Fr *__restrict__ next, Fr *__restrict__ sib_out,
-                                                                unsigned long long *err) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= k) return;
-    const uint64_t node = idx[j] >> l;
-    const uint32_t pj = prev[j];
-    const Fr *from = zero_l;
-    if (pj != MU_NONE) from = cur + pj;
-    else {
-        const uint64_t s = smt_find(tkeys, log_cap, node ^ 1, err);
-        if (s != SMT_NOT_FOUND) from = tvals + s;
+    __device__ __forceinline__ const Fr *get(uint64_t key) const {
+        const uint64_t s = smt_find(keys, log_cap, key, err);
+        return s != SMT_NOT_FOUND ? vals + s : zero_l;
     }
-    const Fr sib = *from;
-    const Fr own = cur[j];
-    if (sib_out) sib_out[(size_t)j * depth] = sib;
-    const bool right = node & 1;
-    Fr x, y;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { x.v[i] = right ? sib.v[i] : own.v[i]; y.v[i] = right ? own.v[i] : sib.v[i]; }
-    next[j] = hash2(tab, f, p, x, y);
-}
-
-// the last write of each run leaves its value in the level's table
-__global__ __launch_bounds__(POS_THREADS) void smt_write_back_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ord, uint32_t k,
-                                                                      const Fr *__restrict__ cur, uint64_t *__restrict__ tkeys, Fr *__restrict__ tvals, uint32_t log_cap,
-                                                                      unsigned long long *count, unsigned long long *err) {
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= k) return;
-    const uint64_t node = keys[q];
-    if (q + 1 != k && keys[q + 1] == node) return;
-    const uint64_t s = smt_claim(tkeys, log_cap, node, count, err);
-    if (s != SMT_NOT_FOUND) tvals[s] = cur[ord[q]];
-}
+};
 
 // read only.  One lane per (proof, level): lane i * depth + l stores the sibling of indices[i] at level l
 __global__ __launch_bounds__(POS_THREADS) void smt_siblings_kernel(SmtTables tabs, const Fr *__restrict__ zero, uint32_t depth, const uint64_t *__restrict__ idx, uint64_t total,
@@ -303,87 +245,40 @@ static size_t smt_device_bytes(const fk_smt *t) {
     return b;
 }
 
-// k >= 1, arguments checked, the staging claimed.  ms: null, or where the timed entry wants the device times (then the call waits for the stream)
-static int smt_update_dev(fk_ctx *ctx, fk_smt *t, const uint64_t *d_idx, const Fr *d_new, uint32_t k, Fr *d_old, Fr *d_sib, Fr *d_roots, double *ms) {
-    const uint32_t depth = t->depth;
-    const dim3 grid(pos_blocks(k)), block(POS_THREADS);
+static SmtStore smt_store(const fk_smt *t, uint32_t l) {
+    const fk_smt::Level &v = t->lv[l];
+    return SmtStore{v.keys, v.vals, v.log_cap, t->d_zero + l, t->d_meta + l, t->d_meta + SMT_META_ERR};
+}
+
+// what the update and the set share in front of their levels: the tree usable, the indices good
+static int smt_write_head(fk_ctx *ctx, fk_smt *t, const uint64_t *d_idx, uint32_t k, const char *what, const char *tail) {
     FK_TRY(smt_take_counts(ctx, t, false));
     FK_TRY(smt_usable(ctx, t));
     // the indices first: nothing is written, and no table grows, before they are known to be good
     PosDev d; FK_TRY(misc_head(ctx, nullptr, nullptr, 0, &d));
-    FK_HIP(ctx, hipMemsetAsync(d.flag, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(mu_check_kernel, grid, block, 0, ctx->stream, d_idx, k, depth, d.flag);
-    FK_HIP(ctx, hipGetLastError());
-    uint32_t bad = 0;
-    FK_HIP(ctx, hipMemcpyAsync(&bad, d.flag, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (bad) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "sparse merkle: a leaf index of the update is not below 2^%u (nothing was written: the tree and the outputs are as they were)", depth);
+    return ms_check_indices(ctx, d.flag, d_idx, k, t->depth, "sparse merkle", what, tail);
+}
 
-    unsigned long long *err = t->d_meta + SMT_META_ERR;
-    if (depth == 0) {       // the tree is its root
-        if (d_old) hipLaunchKernelGGL(smt_depth0_old_kernel, grid, block, 0, ctx->stream, (const Fr *)t->d_root, d_new, k, d_old);
-        FK_HIP(ctx, hipGetLastError());
-        if (d_roots) FK_HIP(ctx, hipMemcpyAsync(d_roots, d_new, (size_t)k * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-        FK_HIP(ctx, hipMemcpyAsync(t->d_root, d_new + (k - 1), sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-        if (ms) { FK_HIP(ctx, hipStreamSynchronize(ctx->stream)); ms[0] = ms[1] = 0; }
-        return FK_OK;
-    }
-
-    size_t sort_bytes = 0;
-    uint64_t *keys = nullptr, *next_keys = nullptr;
-    uint32_t *ord = nullptr, *next_ord = nullptr, *prev = nullptr;
-    FK_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, d_idx, keys, (const uint32_t *)next_ord, ord, (size_t)k, 0u, depth, ctx->stream));
-    FK_HIP(ctx, ctx->stage_a.reserve((size_t)2 * k * sizeof(Fr)));
-    FK_HIP(ctx, ctx->stage_b.reserve((size_t)k * (2 * sizeof(uint64_t) + 3 * sizeof(uint32_t))));
-    FK_HIP(ctx, ctx->stage_c.reserve(sort_bytes ? sort_bytes : 8));
+// room for the k writes, before anything is written; from here on the tables may hold up to this much more
+static int smt_make_room(fk_ctx *ctx, fk_smt *t, uint32_t k) {
     FK_TRY(smt_settle_capacity(ctx, t, k));
-    Fr *val[2] = {ctx->stage_a.as<Fr>(), ctx->stage_a.as<Fr>() + k};
-    keys = ctx->stage_b.as<uint64_t>(); next_keys = keys + k;
-    ord = (uint32_t *)(next_keys + k); next_ord = ord + k; prev = next_ord + k;
-
-    MuEvents tm;
-    if (ms) { FK_HIP(ctx, tm.make(2 + 2 * (size_t)depth)); FK_HIP(ctx, hipEventRecord(tm.ev[0], ctx->stream)); }
-
-    // from here on the tables may hold up to this much more
-    for (uint32_t l = 0; l < depth; l++) t->lv[l].bound += std::min<uint64_t>(k, smt_level_nodes(depth, l));
-
-    // the level-0 order: a stable sort of (index, j) by the index
-    hipLaunchKernelGGL(mu_iota_kernel, grid, block, 0, ctx->stream, next_ord, k);
-    FK_HIP(ctx, hipGetLastError());
-    FK_HIP(ctx, rocprim::radix_sort_pairs(ctx->stage_c.p, sort_bytes, d_idx, keys, (const uint32_t *)next_ord, ord, (size_t)k, 0u, depth, ctx->stream));
-    if (d_old) hipLaunchKernelGGL(smt_old_leaves_kernel, grid, block, 0, ctx->stream, (const uint64_t *)keys, (const uint32_t *)ord, k, (const uint64_t *)t->lv[0].keys,
-                                  (const Fr *)t->lv[0].vals, t->lv[0].log_cap, d_new, d_old, err);
-    FK_HIP(ctx, hipGetLastError());
-    FK_DBG(ctx, "sparse merkle update: sort");
-
-    const Fr *cur = d_new;
-    for (uint32_t l = 0; l < depth; l++) {
-        Fr *next = val[l & 1];
-        const fk_smt::Level &v = t->lv[l];
-        hipLaunchKernelGGL(mu_plan_kernel, grid, block, 0, ctx->stream, (const uint64_t *)keys, (const uint32_t *)ord, k, prev, next_keys, next_ord);
-        if (ms) FK_HIP(ctx, hipEventRecord(tm.ev[2 + 2 * l], ctx->stream));
-        hipLaunchKernelGGL(smt_hash_kernel, grid, block, 0, ctx->stream, (const Fr *)t->d_tab, t->h.f, t->h.p, (const uint64_t *)v.keys, (const Fr *)v.vals, v.log_cap,
-                           (const Fr *)(t->d_zero + l), d_idx, l, depth, (const uint32_t *)prev, cur, k, next, d_sib ? d_sib + l : (Fr *)nullptr, err);
-        if (ms) FK_HIP(ctx, hipEventRecord(tm.ev[3 + 2 * l], ctx->stream));
-        hipLaunchKernelGGL(smt_write_back_kernel, grid, block, 0, ctx->stream, (const uint64_t *)keys, (const uint32_t *)ord, k, cur, v.keys, v.vals, v.log_cap, t->d_meta + l, err);
-        FK_HIP(ctx, hipGetLastError());
-        FK_DBG(ctx, "sparse merkle update: level");
-        std::swap(keys, next_keys); std::swap(ord, next_ord);
-        cur = next;
-    }
-    // every write passes through the root: the last of the list leaves its value there
-    if (d_roots) FK_HIP(ctx, hipMemcpyAsync(d_roots, cur, (size_t)k * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(t->d_root, cur + (k - 1), sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-    if (ms) FK_HIP(ctx, hipEventRecord(tm.ev[1], ctx->stream));
-    FK_TRY(smt_queue_counts(ctx, t));
-    if (ms) {
-        FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float tt = 0;
-        FK_HIP(ctx, hipEventElapsedTime(&tt, tm.ev[0], tm.ev[1]));
-        ms[0] = tt; ms[1] = 0;
-        for (uint32_t l = 0; l < depth; l++) { FK_HIP(ctx, hipEventElapsedTime(&tt, tm.ev[2 + 2 * l], tm.ev[3 + 2 * l])); ms[1] += tt; }
-    }
+    for (uint32_t l = 0; l < t->depth; l++) t->lv[l].bound += ms_level_bound(t->depth, l, k);
     return FK_OK;
+}
+
+// k >= 1, arguments checked, the staging claimed.  ms: null, or where the timed entry wants the device times (then the call waits for the stream)
+static int smt_update_dev(fk_ctx *ctx, fk_smt *t, const uint64_t *d_idx, const Fr *d_new, uint32_t k, Fr *d_old, Fr *d_sib, Fr *d_roots, double *ms) {
+    const uint32_t depth = t->depth;
+    FK_TRY(smt_write_head(ctx, t, d_idx, k, "update", MU_UPDATE_TAIL));
+    if (depth == 0) return mu_update_depth0(ctx, d_new, k, t->d_root, d_old, d_roots, ms);
+    MuScratch s; FK_TRY(mu_reserve(ctx, d_idx, depth, k, &s));
+    MuEvents tm;
+    if (ms) FK_HIP(ctx, tm.make(2 + 2 * (size_t)depth));
+    FK_TRY(smt_make_room(ctx, t, k));
+    auto store_at = [&](uint32_t l) { return smt_store(t, l); };
+    FK_TRY(mu_update_levels(ctx, (const Fr *)t->d_tab, t->h.f, t->h.p, depth, d_idx, d_new, k, s, store_at, t->d_root, d_old, d_sib, d_roots, ms ? &tm : nullptr));
+    FK_TRY(smt_queue_counts(ctx, t));
+    return ms ? mu_finish_timed(ctx, tm, depth, ms) : FK_OK;
 }
 
 static int smt_update_args(fk_ctx *ctx, const fk_smt *t, size_t k) {
@@ -392,54 +287,33 @@ static int smt_update_args(fk_ctx *ctx, const fk_smt *t, size_t k) {
     return FK_OK;
 }
 
-// a level as merkle_plan.hpp's bulk write sees it
-struct SmtStore {
-    uint64_t *keys; Fr *vals; uint32_t log_cap; const Fr *zero_l; unsigned long long *count, *err;
-    __device__ __forceinline__ void put(uint64_t key, const Fr &v) const {
-        const uint64_t s = smt_claim(keys, log_cap, key, count, err);
-        if (s != SMT_NOT_FOUND) vals[s] = v;
-    }
-    __device__ __forceinline__ const Fr *get(uint64_t key) const {
-        const uint64_t s = smt_find(keys, log_cap, key, err);
-        return s != SMT_NOT_FOUND ? vals + s : zero_l;
-    }
-};
-
 // k >= 1, arguments checked, the staging claimed.  timed: null, or what the timed entry wants (then the call waits for the stream)
 static int smt_set_dev(fk_ctx *ctx, fk_smt *t, const uint64_t *d_idx, const Fr *d_leaves, uint32_t k, Fr *d_root, const MsTimed *timed) {
     const uint32_t depth = t->depth;
-    FK_TRY(smt_take_counts(ctx, t, false));
-    FK_TRY(smt_usable(ctx, t));
-    // the indices first: nothing is written, and no table grows, before they are known to be good
-    PosDev d; FK_TRY(misc_head(ctx, nullptr, nullptr, 0, &d));
-    FK_TRY(ms_check_indices(ctx, d.flag, d_idx, k, depth, "sparse merkle"));
+    FK_TRY(smt_write_head(ctx, t, d_idx, k, "set", MS_SET_TAIL));
     if (depth == 0) return ms_set_depth0(ctx, d_leaves, k, t->d_root, d_root, timed);
-
     MsScratch s; FK_TRY(ms_reserve(ctx, d_idx, depth, k, &s));
-    FK_TRY(smt_settle_capacity(ctx, t, k));
     MuEvents tm;
     if (timed) FK_HIP(ctx, tm.make(2 + 2 * (size_t)depth));
-    // from here on the tables may hold up to this much more
-    for (uint32_t l = 0; l < depth; l++) t->lv[l].bound += ms_level_bound(depth, l, k);
-    unsigned long long *err = t->d_meta + SMT_META_ERR;
-    auto store_at = [&](uint32_t l) { const fk_smt::Level &v = t->lv[l]; return SmtStore{v.keys, v.vals, v.log_cap, t->d_zero + l, t->d_meta + l, err}; };
+    FK_TRY(smt_make_room(ctx, t, k));
+    auto store_at = [&](uint32_t l) { return smt_store(t, l); };
     FK_TRY(ms_set_levels(ctx, (const Fr *)t->d_tab, t->h.f, t->h.p, depth, d_idx, d_leaves, k, s, store_at, t->d_root, d_root, timed ? &tm : nullptr));
     FK_TRY(smt_queue_counts(ctx, t));
     if (timed) FK_TRY(ms_finish_timed(ctx, tm, depth, s, *timed));
     return FK_OK;
 }
 
+// the end of a host-array entry that wrote: the counts have arrived with the outputs
+static int smt_host_end(fk_ctx *ctx, fk_smt *t, int rc) {
+    if (rc == FK_OK) rc = smt_take_counts(ctx, t, false);
+    return rc == FK_OK ? smt_usable(ctx, t) : rc;
+}
+
 // n >= 1, arguments checked.  Read only: the tables, `misc` for the flag
 static int smt_proofs_dev(fk_ctx *ctx, const fk_smt *t, const uint64_t *d_idx, size_t n, Fr *d_leaves, Fr *d_sib) {
     const uint32_t depth = t->depth;
     PosDev d; FK_TRY(misc_head(ctx, nullptr, nullptr, 0, &d));
-    FK_HIP(ctx, hipMemsetAsync(d.flag, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(mu_check_kernel, dim3(pos_blocks(n)), dim3(POS_THREADS), 0, ctx->stream, d_idx, (uint32_t)n, depth, d.flag);
-    FK_HIP(ctx, hipGetLastError());
-    uint32_t bad = 0;
-    FK_HIP(ctx, hipMemcpyAsync(&bad, d.flag, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
-    FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (bad) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "sparse merkle: a leaf index of the proofs is not below 2^%u (nothing was written)", depth);
+    FK_TRY(ms_check_indices(ctx, d.flag, d_idx, (uint32_t)n, depth, "sparse merkle", "proofs", ""));
     unsigned long long *err = t->d_meta + SMT_META_ERR;
     if (d_leaves) {
         if (depth == 0) hipLaunchKernelGGL(smt_fill_kernel, dim3(pos_blocks(n)), dim3(POS_THREADS), 0, ctx->stream, d_leaves, (uint64_t)n, (const Fr *)t->d_root);
@@ -568,28 +442,10 @@ int fk_smt_update(fk_ctx *ctx, fk_smt *t, const uint64_t *indices, const uint64_
     if (!k) return FK_OK;
     if (!indices || !new_leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     FK_TRY(scratch_claim(ctx, "sparse merkle update"));
-    // one block: new leaves | old leaves | roots | siblings | indices (the outputs are used only where asked for)
-    const uint32_t depth = t->depth;
-    const size_t ib = k * sizeof(uint64_t), lb = k * sizeof(Fr), sb = siblings ? lb * depth : 0;
-    MuDevBlock blk;
-    FK_HIP(ctx, hipMalloc(&blk.p, 3 * lb + sb + ib));
-    Fr *d_new = (Fr *)blk.p, *d_old = old_leaves ? d_new + k : nullptr, *d_roots = roots ? d_new + 2 * k : nullptr, *d_sib = sb ? d_new + 3 * k : nullptr;
-    uint64_t *d_idx = (uint64_t *)((uint8_t *)blk.p + 3 * lb + sb);
-    FK_HIP(ctx, hipMemcpyAsync(d_idx, indices, ib, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(d_new, new_leaves, lb, hipMemcpyHostToDevice, ctx->stream));
-    int rc = smt_update_dev(ctx, t, d_idx, d_new, (uint32_t)k, d_old, d_sib, d_roots, nullptr);
-    if (rc == FK_OK) {
-        auto down = [&]() -> int {
-            if (d_old) FK_HIP(ctx, hipMemcpyAsync(old_leaves, d_old, lb, hipMemcpyDeviceToHost, ctx->stream));
-            if (d_roots) FK_HIP(ctx, hipMemcpyAsync(roots, d_roots, lb, hipMemcpyDeviceToHost, ctx->stream));
-            if (d_sib) FK_HIP(ctx, hipMemcpyAsync(siblings, d_sib, sb, hipMemcpyDeviceToHost, ctx->stream));
-            return FK_OK;
-        };
-        rc = down();
-    }
-    (void)hipStreamSynchronize(ctx->stream);      // the block is in use until the stream has drained, on the error paths too
-    if (rc == FK_OK) { rc = smt_take_counts(ctx, t, false); if (rc == FK_OK) rc = smt_usable(ctx, t); }      // the counts have arrived with the outputs
-    return rc;
+    MuArray a[] = {{new_leaves, nullptr, k}, {nullptr, old_leaves, k}, {nullptr, roots, k}, {nullptr, siblings, k * t->depth}};
+    return smt_host_end(ctx, t, mu_host_call(ctx, indices, k, a, [&](const uint64_t *d_idx) {
+        return smt_update_dev(ctx, t, d_idx, a[0].d, (uint32_t)k, a[1].d, a[3].d, a[2].d, nullptr);
+    }));
 }); }
 
 int fk_smt_proofs_dev(fk_ctx *ctx, const fk_smt *t, const void *d_indices, size_t n, void *d_leaves, void *d_siblings) { return fk_guard(ctx, [&]() -> int {
@@ -611,24 +467,9 @@ int fk_smt_proofs(fk_ctx *ctx, const fk_smt *t, const uint64_t *indices, size_t 
     if (!indices) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     FK_TRY(smt_usable(ctx, t));
     FK_HIP(ctx, hipSetDevice(ctx->device));
-    // a block of its own (no staging buffer: the call works during an early front): leaves | siblings | indices
-    const size_t ib = n * sizeof(uint64_t), lb = leaves ? n * sizeof(Fr) : 0, sb = siblings ? n * sizeof(Fr) * t->depth : 0;
-    MuDevBlock blk;
-    FK_HIP(ctx, hipMalloc(&blk.p, lb + sb + ib));
-    Fr *d_leaves = lb ? (Fr *)blk.p : nullptr, *d_sib = sb ? (Fr *)((uint8_t *)blk.p + lb) : nullptr;
-    uint64_t *d_idx = (uint64_t *)((uint8_t *)blk.p + lb + sb);
-    FK_HIP(ctx, hipMemcpyAsync(d_idx, indices, ib, hipMemcpyHostToDevice, ctx->stream));
-    int rc = smt_proofs_dev(ctx, t, d_idx, n, d_leaves, d_sib);
-    if (rc == FK_OK) {
-        auto down = [&]() -> int {
-            if (d_leaves) FK_HIP(ctx, hipMemcpyAsync(leaves, d_leaves, lb, hipMemcpyDeviceToHost, ctx->stream));
-            if (d_sib) FK_HIP(ctx, hipMemcpyAsync(siblings, d_sib, sb, hipMemcpyDeviceToHost, ctx->stream));
-            return FK_OK;
-        };
-        rc = down();
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
+    // a block of its own (no staging buffer: the call works during an early front)
+    MuArray a[] = {{nullptr, leaves, n}, {nullptr, siblings, n * t->depth}};
+    return mu_host_call(ctx, indices, n, a, [&](const uint64_t *d_idx) { return smt_proofs_dev(ctx, t, d_idx, n, a[0].d, a[1].d); });
 }); }
 
 int fk_smt_export_level(fk_ctx *ctx, const fk_smt *t, uint32_t level, uint64_t *keys, uint64_t *vals, size_t cap, size_t *n) { return fk_guard(ctx, [&]() -> int {
@@ -694,22 +535,8 @@ int fk_smt_set(fk_ctx *ctx, fk_smt *t, const uint64_t *indices, const uint64_t *
     if (!k) return FK_OK;
     if (!indices || !leaves) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     FK_TRY(scratch_claim(ctx, "sparse merkle set"));
-    // one block: leaves | the root | indices
-    const size_t ib = k * sizeof(uint64_t), lb = k * sizeof(Fr);
-    MuDevBlock blk;
-    FK_HIP(ctx, hipMalloc(&blk.p, lb + sizeof(Fr) + ib));
-    Fr *d_leaves = (Fr *)blk.p, *d_root = d_leaves + k;
-    uint64_t *d_idx = (uint64_t *)(d_root + 1);
-    FK_HIP(ctx, hipMemcpyAsync(d_idx, indices, ib, hipMemcpyHostToDevice, ctx->stream));
-    FK_HIP(ctx, hipMemcpyAsync(d_leaves, leaves, lb, hipMemcpyHostToDevice, ctx->stream));
-    int rc = smt_set_dev(ctx, t, d_idx, d_leaves, (uint32_t)k, root ? d_root : nullptr, nullptr);
-    if (rc == FK_OK && root) {
-        auto down = [&]() -> int { FK_HIP(ctx, hipMemcpyAsync(root, d_root, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream)); return FK_OK; };
-        rc = down();
-    }
-    (void)hipStreamSynchronize(ctx->stream);      // the block is in use until the stream has drained, on the error paths too
-    if (rc == FK_OK) { rc = smt_take_counts(ctx, t, false); if (rc == FK_OK) rc = smt_usable(ctx, t); }      // the counts have arrived with the root
-    return rc;
+    MuArray a[] = {{leaves, nullptr, k}, {nullptr, root, 1}};
+    return smt_host_end(ctx, t, mu_host_call(ctx, indices, k, a, [&](const uint64_t *d_idx) { return smt_set_dev(ctx, t, d_idx, a[0].d, (uint32_t)k, a[1].d, nullptr); }));
 }); }
 
 }  // extern "C"

@@ -53,6 +53,13 @@ class MerkleUpdates:
     def __init__(self, root_before, old_leaves, siblings, roots):
         self.root_before, self.old_leaves, self.siblings, self.roots = root_before, old_leaves, siblings, roots
 
+    @classmethod
+    def from_limbs(cls, root_before, old_leaves, siblings, roots, as_limbs):
+        """from the four limb arrays of a call: kept as they are, or as canonical ints"""
+        if as_limbs:
+            return cls(root_before, old_leaves, siblings, roots)
+        return cls(_fr_ints(root_before)[0], _fr_ints(old_leaves), _sibling_lists(siblings), _fr_ints(roots))
+
     def roots_before(self):
         """the root each write started from: [root_before] + roots[:-1]"""
         if isinstance(self.roots, np.ndarray):
@@ -64,6 +71,19 @@ class MerkleUpdates:
 
     def __repr__(self):
         return 'MerkleUpdates(%d writes)' % len(self)
+
+
+def _writes(indices, leaves):
+    """the arguments of k writes -> (indices (k,) uint64, leaves (k, 4) Montgomery limbs, k, whether the leaves were given as limbs)"""
+    as_limbs = _is_limbs(leaves)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    k = idx.shape[0]
+    return idx, _fr_rows(leaves, k), k, as_limbs
+
+
+def _sibling_lists(sib):
+    """(n, depth, 4) limbs -> n lists of depth canonical ints"""
+    return [_fr_ints(rows) for rows in sib]
 
 
 def update_dev(ctx, params, d_nodes, depth, d_indices, d_leaves, k, d_old, d_sib, d_roots):
@@ -85,17 +105,11 @@ def update(tree, params, indices, leaves):
     ints or an (k, 4) uint64 array of Montgomery limbs.  A refused call (FkError: an index not below 2^depth, t != 3) leaves the tree
     as it was."""
     ctx, depth = tree.ctx, tree.depth
-    as_limbs = _is_limbs(leaves)
-    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-    k = idx.shape[0]
-    la = _fr_rows(leaves, k)
+    idx, la, k, as_limbs = _writes(indices, leaves)
     root = ctx.download(tree.d_nodes + 32 * (tree.n_nodes - 1), 32, np.uint64)
     old, sib, roots = np.zeros((k, 4), np.uint64), np.zeros((k, depth, 4), np.uint64), np.zeros((k, 4), np.uint64)
     ctx._ck(_lib().fk_poseidon_merkle_update(ctx.handle, params.handle, tree.d_nodes, depth, _vp(idx), _vp(la), k, _vp(old), _vp(sib) if depth else None, _vp(roots)))
     if k:
         tree._root = None
         tree.n_leaves = max(tree.n_leaves, int(idx.max()) + 1)
-    if as_limbs:
-        return MerkleUpdates(root, old, sib, roots)
-    flat = _fr_ints(sib)
-    return MerkleUpdates(_fr_ints(root)[0], _fr_ints(old), [flat[j * depth:(j + 1) * depth] for j in range(k)], _fr_ints(roots))
+    return MerkleUpdates.from_limbs(root, old, sib, roots, as_limbs)

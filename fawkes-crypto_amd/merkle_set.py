@@ -16,7 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import api
-from .api import _fr_ints, _fr_rows, _is_limbs, _vp
+from .api import _fr_ints, _vp
+from .merkle import _writes
 
 MAX_WRITES = 1 << 28
 
@@ -67,10 +68,7 @@ def set_sparse(tree, indices, leaves):
     were ints, 4 limbs where they were an (k, 4) uint64 array).  A refused call (FkError: an index not below 2^depth) leaves the tree as
     it was."""
     ctx = tree.ctx
-    as_limbs = _is_limbs(leaves)
-    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-    k = idx.shape[0]
-    la = _fr_rows(leaves, k)
+    idx, la, k, as_limbs = _writes(indices, leaves)
     root = np.zeros(4, np.uint64)
     ctx._ck(_lib().fk_smt_set(ctx.handle, tree.handle, _vp(idx), _vp(la), k, _vp(root)))
     if not k:
@@ -110,10 +108,7 @@ def set_dense(tree, params, indices, leaves):
     leaves were given).  An index at or above tree.n_leaves appends, as there.  A refused call (FkError: an index not below 2^depth,
     t != 3) leaves the tree as it was."""
     ctx, depth = tree.ctx, tree.depth
-    as_limbs = _is_limbs(leaves)
-    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-    k = idx.shape[0]
-    la = _fr_rows(leaves, k)
+    idx, la, k, as_limbs = _writes(indices, leaves)
     ctx._ck(_lib().fk_poseidon_merkle_set(ctx.handle, params.handle, tree.d_nodes, depth, _vp(idx), _vp(la), k))
     if k:
         tree._root = None

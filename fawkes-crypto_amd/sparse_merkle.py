@@ -17,8 +17,8 @@ import ctypes as C
 import numpy as np
 
 from . import api
-from .api import _fr_ints, _fr_rows, _is_limbs, _vp
-from .merkle import MerkleUpdates
+from .api import _fr_ints, _vp
+from .merkle import MerkleUpdates, _sibling_lists, _writes
 
 MAX_DEPTH = 63
 MIN_SLOTS = 64
@@ -126,10 +126,7 @@ class SparseMerkleTree(api._Handle):
         n, depth = idx.shape[0], self.depth
         lv, sib = np.zeros((n, 4), np.uint64), np.zeros((n, depth, 4), np.uint64)
         self.ctx._ck(_lib().fk_smt_proofs(self.ctx.handle, self.handle, _vp(idx), n, _vp(lv), _vp(sib) if depth else None))
-        if as_limbs:
-            return lv, sib
-        flat = _fr_ints(sib)
-        return _fr_ints(lv), [flat[i * depth:(i + 1) * depth] for i in range(n)]
+        return (lv, sib) if as_limbs else (_fr_ints(lv), _sibling_lists(sib))
 
     # ---- writing
     def update_dev(self, d_indices, d_leaves, k, d_old, d_sib, d_roots):
@@ -147,17 +144,11 @@ class SparseMerkleTree(api._Handle):
         were ints, limb arrays where they were an (k, 4) uint64 array).  A refused call (FkError: an index not below 2^depth) leaves
         the tree as it was."""
         ctx, depth = self.ctx, self.depth
-        as_limbs = _is_limbs(leaves)
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-        k = idx.shape[0]
-        la = _fr_rows(leaves, k)
+        idx, la, k, as_limbs = _writes(indices, leaves)
         root = self.root_limbs()
         old, sib, roots = np.zeros((k, 4), np.uint64), np.zeros((k, depth, 4), np.uint64), np.zeros((k, 4), np.uint64)
         ctx._ck(_lib().fk_smt_update(ctx.handle, self.handle, _vp(idx), _vp(la), k, _vp(old), _vp(sib) if depth else None, _vp(roots)))
-        if as_limbs:
-            return MerkleUpdates(root, old, sib, roots)
-        flat = _fr_ints(sib)
-        return MerkleUpdates(_fr_ints(root)[0], _fr_ints(old), [flat[j * depth:(j + 1) * depth] for j in range(k)], _fr_ints(roots))
+        return MerkleUpdates.from_limbs(root, old, sib, roots, as_limbs)
 
     # ---- bulk writes (merkle_set.py, imported where it is used: that module imports this one's class)
     def set(self, indices, leaves):

@@ -2,6 +2,7 @@
 in-order walk on the oracle's poseidon (tests/merkle_cases.py): old leaves, every sibling, every root and ALL nodes of the final tree;
 device-only consistency at a size the oracle cannot reach; NULL outputs, refusals, the empty call, the cached root; and one batch of
 chained transactions from the update's output to a checked proof.  Every comparison is exact equality of canonical integers or bytes."""
+import itertools
 import random
 
 import numpy as np
@@ -22,6 +23,8 @@ pytestmark = pytest.mark.gpu
 R = ref.R
 TOX = {k: fx.mont_fr(v) for k, v in TOXIC.items()}
 MARK = 0xa5a5a5a5a5a5a5a5
+OUTPUTS = ('old', 'sib', 'roots')
+SUBSETS = [s for n in range(4) for s in itertools.combinations(OUTPUTS, n)]
 
 
 @pytest.fixture(scope='module')
@@ -157,20 +160,44 @@ def test_depth12_5000_writes_are_consistent_on_the_device(ctx, p3):
 
 
 # ---------------------------------------------------------------- NULL outputs, refusals, the empty call, the cached root
-@pytest.mark.parametrize('outputs', [('sib', 'roots'), ('old', 'roots'), ('old', 'sib'), ()])
+@pytest.mark.parametrize('outputs', SUBSETS)
 def test_null_outputs_leave_the_same_tree(ctx, p3, outputs):
     c = mc.case('hot', 65)
     tree = ctx.merkle_tree(p3, c.leaves)
     a = run_dev(ctx, p3, tree, c.indices, c.values, outputs)
     try:
         assert node_ints(tree) == c.nodes
-        for n in ('old', 'sib', 'roots'):                               # what was not asked for was not written
+        for n in OUTPUTS:                                               # what was not asked for was not written
             if n not in outputs:
                 assert (a.get(n) == MARK).all()
         if 'roots' in outputs:
             assert fk.api._fr_ints(a.get('roots')) == c.roots
         if 'old' in outputs:
             assert fk.api._fr_ints(a.get('old')) == c.old
+        if 'sib' in outputs:
+            assert fk.api._fr_ints(a.get('sib')) == [s for row in c.siblings for s in row]
+    finally:
+        a.free()
+        tree.free()
+
+
+@pytest.mark.parametrize('k', [3, 1])
+@pytest.mark.parametrize('outputs', SUBSETS)
+def test_depth0_device_arrays_equal_the_walk(ctx, p3, outputs, k):
+    """the tree is its root: write j replaces what write j - 1 left (the first k writes of the case are the walk of those k alone)"""
+    c = mc.case('depth0')
+    assert c.depth == 0 and c.indices == [0, 0, 0]
+    tree = ctx.merkle_tree(p3, c.leaves)
+    a = run_dev(ctx, p3, tree, c.indices[:k], c.values[:k], outputs)
+    try:
+        assert node_ints(tree) == [c.roots[k - 1]]
+        for n in OUTPUTS:
+            if n not in outputs:
+                assert (a.get(n) == MARK).all()
+        if 'roots' in outputs:
+            assert fk.api._fr_ints(a.get('roots')) == c.roots[:k]
+        if 'old' in outputs:
+            assert fk.api._fr_ints(a.get('old')) == c.old[:k]
     finally:
         a.free()
         tree.free()

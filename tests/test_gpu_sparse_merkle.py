@@ -330,6 +330,28 @@ def test_null_outputs_leave_the_same_tree(ctx, p3, outputs):
         tree.free()
 
 
+@pytest.mark.parametrize('k', [3, 1])
+@pytest.mark.parametrize('outputs', [s for n in range(4) for s in itertools.combinations(OUTPUTS, n)])
+def test_depth0_device_arrays_equal_the_walk(ctx, p3, outputs, k):
+    """the tree is its root: write j replaces what write j - 1 left (the first k writes of the case are the walk of those k alone)"""
+    c = mc.case('depth0')
+    assert c.depth == 0 and c.indices == [0, 0, 0]
+    tree = sparse_from_dense_case(ctx, p3, c)
+    a = run_dev(ctx, tree, c.indices[:k], c.values[:k], outputs)
+    try:
+        assert tree.root == c.roots[k - 1] and tree.level(0) == {0: c.roots[k - 1]}
+        for n in OUTPUTS:
+            if n not in outputs:
+                assert a.marked(n)
+        if 'roots' in outputs:
+            assert ints(a.get('roots')) == c.roots[:k]
+        if 'old' in outputs:
+            assert ints(a.get('old')) == c.old[:k]
+    finally:
+        a.free()
+        tree.free()
+
+
 def _state(tree):
     return tree.root, tree.info(), [tree.level(l) for l in range(tree.depth + 1)]
 
