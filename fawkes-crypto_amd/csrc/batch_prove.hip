@@ -16,7 +16,7 @@
 #include "common.hpp"
 #include "ntt_domain.hpp"
 #include "r1cs.hpp"
-#include "../../include/fawkes_hip_batch.h"
+#include "batch_shared.hpp"
 #include <rocprim/device/device_scan.hpp>
 #include <chrono>
 #include <string.h>
@@ -26,23 +26,6 @@ using namespace fk;
 namespace fk {
 
 static_assert(FK_BATCH_MAX_GROUP <= 65535, "the proof index is gridDim.y");
-
-// ------------------------------------------------------------------------------------------ where a variable lives
-// ONE function of (layout, proof, variable): every stage that reads z goes through it.
-struct ZView {
-    const Fr *z;
-    int layout;
-    uint32_t num_input, num_aux;     // FK_BATCH_Z_TILED
-    uint32_t count, p0;              // proofs of the whole call (the tiled order depends on it); first proof of this group
-    uint64_t row;                    // FK_BATCH_Z_ROWS: elements per row
-};
-static __device__ __forceinline__ uint64_t zaddr(const ZView &v, uint32_t proof, uint32_t var) {
-    const uint64_t p = (uint64_t)v.p0 + proof;
-    if (v.layout == FK_BATCH_Z_ROWS) return p * v.row + var;
-    if (var == 0) return 0;
-    if (var < v.num_input) return 1 + p * (v.num_input - 1) + (var - 1);
-    return 1 + (uint64_t)v.count * (v.num_input - 1) + p * v.num_aux + (var - v.num_input);
-}
 
 // ------------------------------------------------------------------------------------------ evaluation
 struct BatchEvalArgs {
@@ -69,6 +52,13 @@ __global__ __launch_bounds__(256) void batch_eval_kernel(BatchEvalArgs a, const 
         acc = zv.z[zaddr(zv, p, (uint32_t)(t - num_gates))];       // bellman's extra rows: input_i * 0 = 0
     }
     a.out[mtx][(uint64_t)p * m + t] = acc;
+}
+
+static BatchEvalArgs bt_eval_args(const fk_r1cs_dev *r, Fr *a, Fr *b, Fr *c) {
+    BatchEvalArgs ea;
+    for (int k = 0; k < 3; k++) { ea.ptr[k] = r->ptr[k]; ea.col[k] = r->col[k]; ea.cidx[k] = r->cidx[k]; }
+    ea.out[0] = a; ea.out[1] = b; ea.out[2] = c;
+    return ea;
 }
 
 // zero behind the rows (fk_batch_quotient_dev: the caller's arrays); grid (ceil((m - n) / 256), proofs, 3)
@@ -349,7 +339,7 @@ static int bt_budget(fk_ctx *ctx, const fk_batch_opts *opts, fk_batch_opts *eff)
     size_t free_b = 0, total_b = 0;
     FK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
     size_t held = 0;
-    for (const DevBuf *b : {&ctx->bt_vec, &ctx->bt_sort, &ctx->bt_entries, &ctx->bt_partial, &ctx->bt_wsum, &ctx->bt_io, &ctx->bt_scan}) held += b->cap;
+    for (const DevBuf *b : {&ctx->bt_vec, &ctx->bt_sort, &ctx->bt_entries, &ctx->bt_partial, &ctx->bt_wsum, &ctx->bt_io, &ctx->bt_scan, &ctx->bt_check}) held += b->cap;
     eff->scratch_budget_bytes = (free_b + held) / FK_BATCH_BUDGET_FREE_DIVISOR;
     if (!eff->scratch_budget_bytes) eff->scratch_budget_bytes = 1;
     return FK_OK;
@@ -377,12 +367,17 @@ struct BtEvents {
     ~BtEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// sink, check_ms: null for the unchecked entries.  With a sink the per-proof check (batch_check.hip) is queued between the evaluation and
+// the quotient of each group, and the group's reports come down with the group's proofs.
 static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, int z_layout, uint32_t count,
-                                const uint64_t *rr, const uint64_t *ss, uint8_t *out_proofs, const fk_batch_opts *opts, fk_batch_timings *tm) {
-    const char *who = "fk_prove_batch_dev";
+                                const uint64_t *rr, const uint64_t *ss, uint8_t *out_proofs, const fk_batch_opts *opts, fk_batch_timings *tm,
+                                const BatchCheckSink *sink = nullptr, double *check_ms = nullptr) {
+    const char *who = sink ? "fk_prove_batch_checked_dev" : "fk_prove_batch_dev";
     if (tm) memset(tm, 0, sizeof *tm);
+    if (check_ms) *check_ms = 0;
     if (count == 0) return FK_OK;
     if (!key || !r || !d_z || !rr || !ss || !out_proofs) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: null argument", who);
+    if (sink && !sink->reports) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: null reports", who);
     FK_TRY(bt_check_layout(ctx, z_layout, who));
     if (r->copies > 1) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: a tiled system makes ONE proof of its %u copies; load one instance (fk_r1cs_load)", who, r->copies);
     if (key->shard_count != 1) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: a sharded key (%u of %u)", who, key->shard_index, key->shard_count);
@@ -405,7 +400,7 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
     NttDomain *dom = nullptr;
     FK_TRY(get_domain(ctx, log_m, &dom));
     BtEvents evs;
-    if (tm) FK_TRY(evs.init(ctx));
+    if (tm || check_ms) FK_TRY(evs.init(ctx));
     // scratch of one group
     FK_HIP(ctx, ctx->bt_vec.reserve(6 * (size_t)G * m * sizeof(Fr)));
     Fr *va = ctx->bt_vec.as<Fr>(), *vb = va + (size_t)G * m, *vc = vb + (size_t)G * m, *vh = vc + (size_t)G * m, *s1 = vh + (size_t)G * m, *s2 = s1 + (size_t)G * m;
@@ -414,10 +409,9 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
     const size_t io_r = 0, io_s = up256((size_t)G * sizeof(Fr)), io_parts = 2 * io_s, io_out = io_parts + up256((size_t)G * FK_MSM_RESULT_BYTES);
     FK_HIP(ctx, ctx->bt_io.reserve(io_out + (size_t)G * FK_PROOF_BYTES));
     uint8_t *io = ctx->bt_io.as<uint8_t>();
+    if (sink) FK_TRY(batch_check_reserve(ctx, G));
     const AssembleKey ak = key->assemble_key();
-    BatchEvalArgs ea;
-    for (int k = 0; k < 3; k++) { ea.ptr[k] = r->ptr[k]; ea.col[k] = r->col[k]; ea.cidx[k] = r->cidx[k]; }
-    ea.out[0] = va; ea.out[1] = vb; ea.out[2] = vc;
+    const BatchEvalArgs ea = bt_eval_args(r, va, vb, vc);
 
     for (uint32_t g0 = 0; g0 < count; g0 += G) {
         const uint32_t g = std::min(G, count - g0);
@@ -428,6 +422,10 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
         hipLaunchKernelGGL(batch_eval_kernel, dim3((unsigned)((m + 255) / 256), g, 3), dim3(256), 0, ctx->stream, ea, (const Fr *)r->table, zv, r->num_gates, rows, m);
         FK_HIP(ctx, hipGetLastError());
         FK_TRY(evs.mark(ctx, 1));
+        if (sink) {     // a, b, c are whole and the quotient has not touched them yet; events 1 .. 9 bracket the check alone
+            FK_TRY(batch_check_queue(ctx, *sink, zv, va, vb, vc, r->num_gates, m, g));
+            FK_TRY(evs.mark(ctx, 9));
+        }
         FK_TRY(quotient_rows(ctx, dom, va, vb, vc, g, s1, s2, vh));
         FK_TRY(evs.mark(ctx, 2));
         uint8_t *parts = io + io_parts;
@@ -470,11 +468,17 @@ static int prove_batch_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_de
         FK_TRY(evs.mark(ctx, 8));
         // the one place the host blocks: this group's proofs
         FK_HIP(ctx, hipMemcpyAsync(out_proofs + (size_t)g0 * FK_PROOF_BYTES, io + io_out, (size_t)g * FK_PROOF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+        if (sink) FK_TRY(batch_check_download(ctx, *sink, g0, g));
         FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (tm) {
             double *slot[8] = {&tm->eval_ms, &tm->quotient_ms, &tm->msm_h_ms, &tm->msm_l_ms, &tm->msm_a_ms, &tm->msm_b1_ms, &tm->msm_b2_ms, &tm->assemble_ms};
-            for (int i = 0; i < 8; i++) { float ms = 0; FK_HIP(ctx, hipEventElapsedTime(&ms, evs.ev[i], evs.ev[i + 1])); *slot[i] += ms; }
+            for (int i = 0; i < 8; i++) {
+                float ms = 0;
+                FK_HIP(ctx, hipEventElapsedTime(&ms, evs.ev[i == 1 && sink ? 9 : i], evs.ev[i + 1]));      // the quotient begins behind the check
+                *slot[i] += ms;
+            }
         }
+        if (sink && check_ms) { float ms = 0; FK_HIP(ctx, hipEventElapsedTime(&ms, evs.ev[1], evs.ev[9])); *check_ms += ms; }
     }
     if (tm) tm->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return FK_OK;
@@ -508,6 +512,67 @@ int fk_prove_batch(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r1cs, cons
     return prove_batch_dev_impl(ctx, key, r1cs, ctx->bt_z.p, FK_BATCH_Z_ROWS, count, r, s, out_proofs, opts, tm);
 }); }
 
+int fk_prove_batch_checked_dev(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r1cs, const void *d_z, int z_layout, uint32_t count,
+                               const uint64_t *r, const uint64_t *s, uint8_t *out_proofs, const fk_batch_opts *opts, fk_batch_timings *tm,
+                               void *d_bad_bitmap, void *d_proof_bad, fk_check_report *reports, double *check_ms) { return fk_guard(ctx, [&]() -> int {
+    FK_RANGE("fk_prove_batch_checked_dev");
+    if (!ctx) return FK_ERR_BAD_ARG;
+    const BatchCheckSink sink{(unsigned long long *)d_bad_bitmap, (uint8_t *)d_proof_bad, reports};
+    return prove_batch_dev_impl(ctx, key, r1cs, d_z, z_layout, count, r, s, out_proofs, opts, tm, &sink, check_ms);
+}); }
+
+int fk_prove_batch_checked(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r1cs, const uint64_t *z, uint32_t count,
+                           const uint64_t *r, const uint64_t *s, uint8_t *out_proofs, const fk_batch_opts *opts, fk_batch_timings *tm,
+                           void *d_bad_bitmap, void *d_proof_bad, fk_check_report *reports, double *check_ms) { return fk_guard(ctx, [&]() -> int {
+    FK_RANGE("fk_prove_batch_checked");
+    if (!ctx) return FK_ERR_BAD_ARG;
+    if (count == 0) { if (tm) memset(tm, 0, sizeof *tm); if (check_ms) *check_ms = 0; return FK_OK; }
+    if (!key || !r1cs || !z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "fk_prove_batch_checked: null argument");
+    if (!reports) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "fk_prove_batch_checked: null reports");
+    FK_TRY(bt_claim(ctx, "fk_prove_batch_checked"));
+    const size_t bytes = (size_t)count * ((size_t)r1cs->num_input + r1cs->num_aux) * sizeof(Fr);
+    FK_HIP(ctx, ctx->bt_z.reserve(bytes));
+    FK_HIP(ctx, hipMemcpyAsync(ctx->bt_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const BatchCheckSink sink{(unsigned long long *)d_bad_bitmap, (uint8_t *)d_proof_bad, reports};
+    return prove_batch_dev_impl(ctx, key, r1cs, ctx->bt_z.p, FK_BATCH_Z_ROWS, count, r, s, out_proofs, opts, tm, &sink, check_ms);
+}); }
+
+int fk_batch_r1cs_check_dev(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, int z_layout, uint32_t count, void *d_bad_bitmap, void *d_proof_bad,
+                            fk_check_report *reports, const fk_batch_opts *opts) { return fk_guard(ctx, [&]() -> int {
+    const char *who = "fk_batch_r1cs_check_dev";
+    FK_RANGE("fk_batch_r1cs_check_dev");
+    if (!ctx) return FK_ERR_BAD_ARG;
+    if (count == 0) return FK_OK;
+    if (!r || !d_z) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: null argument", who);
+    if (!reports) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: null reports", who);
+    FK_TRY(bt_check_layout(ctx, z_layout, who));
+    if (r->copies > 1) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: a tiled system", who);
+    FK_TRY(bt_claim(ctx, who));
+    fk_batch_opts eff;
+    FK_TRY(bt_budget(ctx, opts, &eff));
+    const uint64_t rows = r->num_gates + r->num_input, m = (uint64_t)1 << ceil_log2_u64(rows);
+    if (m >= ((uint64_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: one proof's rows do not fit 31-bit indices", who);
+    // the largest group whose three rows and records fit the budget (the header states the rule); a group of one is always allowed
+    const uint64_t per_proof = 3 * m * sizeof(Fr) + FK_BATCH_CHECK_RECORD_BYTES;
+    const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>(count, FK_BATCH_MAX_GROUP), (((uint64_t)1 << 31) - 1) / m);
+    const uint32_t G = (uint32_t)std::max<uint64_t>(1, std::min(cap, eff.scratch_budget_bytes / per_proof));
+    FK_HIP(ctx, ctx->bt_vec.reserve(3 * (size_t)G * m * sizeof(Fr)));
+    FK_TRY(batch_check_reserve(ctx, G));
+    Fr *va = ctx->bt_vec.as<Fr>(), *vb = va + (size_t)G * m, *vc = vb + (size_t)G * m;
+    const BatchEvalArgs ea = bt_eval_args(r, va, vb, vc);
+    const BatchCheckSink sink{(unsigned long long *)d_bad_bitmap, (uint8_t *)d_proof_bad, reports};
+    for (uint32_t g0 = 0; g0 < count; g0 += G) {
+        const uint32_t g = std::min(G, count - g0);
+        const ZView zv{(const Fr *)d_z, z_layout, r->num_input, r->num_aux, count, g0, (uint64_t)r->num_input + r->num_aux};
+        hipLaunchKernelGGL(batch_eval_kernel, dim3((unsigned)((m + 255) / 256), g, 3), dim3(256), 0, ctx->stream, ea, (const Fr *)r->table, zv, r->num_gates, rows, m);
+        FK_HIP(ctx, hipGetLastError());
+        FK_TRY(batch_check_queue(ctx, sink, zv, va, vb, vc, r->num_gates, m, g));
+        FK_TRY(batch_check_download(ctx, sink, g0, g));
+        FK_HIP(ctx, hipStreamSynchronize(ctx->stream));         // the one place the host blocks: this group's reports
+    }
+    return FK_OK;
+}); }
+
 int fk_batch_r1cs_eval_dev(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, int z_layout, uint32_t count, void *d_a, void *d_b, void *d_c) { return fk_guard(ctx, [&]() -> int {
     const char *who = "fk_batch_r1cs_eval_dev";
     if (!ctx) return FK_ERR_BAD_ARG;
@@ -518,9 +583,7 @@ int fk_batch_r1cs_eval_dev(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, i
     if (count > FK_BATCH_MAX_GROUP) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: more than %d proofs in one group", who, FK_BATCH_MAX_GROUP);
     FK_TRY(bt_claim(ctx, who));
     const uint64_t rows = r->num_gates + r->num_input, m = (uint64_t)1 << ceil_log2_u64(rows);
-    BatchEvalArgs ea;
-    for (int k = 0; k < 3; k++) { ea.ptr[k] = r->ptr[k]; ea.col[k] = r->col[k]; ea.cidx[k] = r->cidx[k]; }
-    ea.out[0] = (Fr *)d_a; ea.out[1] = (Fr *)d_b; ea.out[2] = (Fr *)d_c;
+    const BatchEvalArgs ea = bt_eval_args(r, (Fr *)d_a, (Fr *)d_b, (Fr *)d_c);
     const ZView zv{(const Fr *)d_z, z_layout, r->num_input, r->num_aux, count, 0, (uint64_t)r->num_input + r->num_aux};
     hipLaunchKernelGGL(batch_eval_kernel, dim3((unsigned)((m + 255) / 256), count, 3), dim3(256), 0, ctx->stream, ea, (const Fr *)r->table, zv, r->num_gates, rows, m);
     FK_HIP(ctx, hipGetLastError());

@@ -17,11 +17,10 @@
 #include <string.h>
 
 #include "r1cs.hpp"
+#include "check_shared.hpp"
 #include "../../include/fawkes_hip_check.h"
 
 namespace fk {
-
-static constexpr unsigned long long CHECK_NONE = ~0ull;
 
 // device-side record of one check; the head of ctx->check
 struct CheckCounters {
@@ -31,17 +30,6 @@ struct CheckCounters {
 };
 static constexpr size_t CHECK_HEAD = 256;
 static_assert(sizeof(CheckCounters) <= CHECK_HEAD, "the counters fit the head of the scratch");
-
-// the 256-bit image is below r (the borrow of x - r)
-static FK_HD bool image_below_r(const Fr &x) {
-    uint32_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const uint64_t t = (uint64_t)x.v[i] - FrParams::p(i) - br;
-        br = (uint32_t)(t >> 63);
-    }
-    return br != 0;
-}
 
 __global__ void check_init_kernel(CheckCounters *cnt) {
     if (blockIdx.x || threadIdx.x) return;
@@ -67,9 +55,7 @@ __global__ __launch_bounds__(256) void check_range_kernel(const Fr *z, uint64_t 
     }
 }
 
-// One gate per lane: one Montgomery product, then a limb compare with c.  field.hpp keeps every value canonical (Fr::mul ends with the
-// conditional subtraction, the evaluation's sums reduce below r), so equality in the field IS equality of the eight limbs -- no
-// subtraction, no second representative to try.  A block is four waves of 64 consecutive gates, so lane 0 of a wave sits on gate
+// One gate per lane: product_differs (check_shared.hpp).  A block is four waves of 64 consecutive gates, so lane 0 of a wave sits on gate
 // 64 * w and the wave's ballot is word w of the bitmap: one ordinary vector store from that lane, and the lanes behind the last gate
 // contribute zero bits.  n_bad and first_bad: popcount and lowest set bit of the ballot, one atomic add and one atomic min per wave
 // that has a bad gate -- a satisfied system issues no atomic at all.  Group flags: a bad lane stores 1 into its group's byte (zeroed
@@ -80,7 +66,7 @@ __global__ __launch_bounds__(256) void check_gates_kernel(const Fr *a, const Fr 
                                                            unsigned long long *bitmap, uint8_t *group_bad, CheckCounters *cnt) {
     const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     bool bad = false;
-    if (g < gates) bad = Fr::mul(a[g], b[g]) != c[g];
+    if (g < gates) bad = product_differs(a[g], b[g], c[g]);
     const unsigned long long word = __ballot(bad);
     if (bad && group_bad) group_bad[g / group_rows] = 1;
     if ((threadIdx.x & 63) == 0 && g < gates) {
@@ -191,15 +177,8 @@ static int r1cs_check_host(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, cons
     if (!cs || !z_ || !rep) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: null argument");
     if (!copies) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: copies = 0");
     if (group_bad && !group_rows) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: group flags asked for with group_rows = 0");
-    if (!cs->num_input) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: a system has the input ONE");
-    const struct { const uint64_t *ptr; const uint32_t *col; const uint64_t *val; } mats[3] = {
-        {cs->a_ptr, cs->a_col, cs->a_val}, {cs->b_ptr, cs->b_col, cs->b_val}, {cs->c_ptr, cs->c_col, cs->c_val}};
-    const uint64_t base_nv = (uint64_t)cs->num_input + cs->num_aux;
-    for (const auto &mt : mats) {
-        if (!mt.ptr) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: null row pointer");
-        for (uint64_t k = mt.ptr[0]; k < mt.ptr[cs->num_gates]; k++)
-            if (mt.col[k] >= base_nv) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: variable index %u out of range", mt.col[k]);
-    }
+    CsrView mats[3];
+    FK_TRY(check_host_system(ctx, cs, mats));
     const uint64_t G = cs->num_gates, gates = G * copies;
     const uint64_t num_input = 1 + (uint64_t)copies * (cs->num_input - 1), n_vars = num_input + (uint64_t)copies * cs->num_aux;
     if (n_vars > 0xffffffffull) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "check: the batch does not fit 32-bit variable indices");
@@ -222,21 +201,9 @@ static int r1cs_check_host(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, cons
         const uint64_t in_off = (uint64_t)copy * (cs->num_input - 1), aux_off = num_input + (uint64_t)copy * cs->num_aux - cs->num_input;
         for (uint64_t row = 0; row < G; row++) {
             Fr abc[3];
-            for (int m = 0; m < 3; m++) {
-                Fr acc = Fr::zero();
-                for (uint64_t k = mats[m].ptr[row]; k < mats[m].ptr[row + 1]; k++) {
-                    uint64_t v = mats[m].col[k];
-                    if (v) v += v < cs->num_input ? in_off : aux_off;
-                    Fr t = z[v];
-                    if (mats[m].val) {                  // NULL: every coefficient of this matrix is ONE
-                        Fr cf; memcpy(&cf, mats[m].val + 4 * k, 32);
-                        if (cf != one) t = Fr::mul(t, cf);
-                    }
-                    acc = Fr::add(acc, t);
-                }
-                abc[m] = acc;
-            }
-            if (Fr::mul(abc[0], abc[1]) == abc[2]) continue;
+            for (int m = 0; m < 3; m++)
+                abc[m] = csr_row_dot(mats[m], row, z, [&](uint64_t v) { return v ? v + (v < cs->num_input ? in_off : aux_off) : 0; });
+            if (!product_differs(abc[0], abc[1], abc[2])) continue;
             const uint64_t g = (uint64_t)copy * G + row;
             if (!rep->n_bad++) { rep->first_bad = g; memcpy(rep->first_abc, abc, sizeof rep->first_abc); }
             if (bad_bitmap) bad_bitmap[g >> 6] |= (uint64_t)1 << (g & 63);

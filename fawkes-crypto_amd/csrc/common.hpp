@@ -47,6 +47,7 @@ struct CtxScratch {
     // staging buffers and the lanes as it left them.  bt_vec: a, b, c, h and the transforms' two intermediates (6 x group x m);
     // bt_z: the witnesses of fk_prove_batch (host rows); bt_sort: histogram, bucket and segment offsets; bt_io: r, s, the five sums per proof, the proofs
     DevBuf bt_vec, bt_z, bt_sort, bt_entries, bt_partial, bt_wsum, bt_io, bt_scan;
+    DevBuf bt_check;  // batch_check.hip: one record (fk_check_report) per proof of a group
     DevBuf *begin() { return &misc; }
     DevBuf *end() { return begin() + sizeof(CtxScratch) / sizeof(DevBuf); }
     void release_scratch() { for (DevBuf *b = begin(); b != end(); ++b) b->release(); }
