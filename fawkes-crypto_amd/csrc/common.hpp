@@ -35,6 +35,27 @@ struct DevBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
+// An exactly-sized device array that frees itself (DevBuf above is scratch: grow-only, with slack, released by hand): what a resident
+// object keeps for its lifetime.  Move-only; converts to the raw pointer that kernel arguments carry.
+template <class T>
+struct DevArr {
+    T *p = nullptr;
+    DevArr() = default;
+    DevArr(DevArr &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevArr &operator=(DevArr &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    DevArr(const DevArr &) = delete;
+    DevArr &operator=(const DevArr &) = delete;
+    ~DevArr() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    hipError_t alloc(size_t n) {        // n elements, whatever it held before is freed
+        reset();
+        const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); }
+        return e;
+    }
+    operator T *() const { return p; }
+};
+
 // The context's grow-only scratch as ONE set: fk_free and fk_trim walk it, so a buffer added here is released by both.  DevBuf members
 // only (the walk below is over them); the MSM lanes keep their own (MsmLane, msm_release).
 struct CtxScratch {

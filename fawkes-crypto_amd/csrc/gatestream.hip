@@ -28,6 +28,7 @@
 // in this image and on the GPU box -- bound at run time with dlopen: the format's 122 KB static dictionary makes a private codec
 // pointless.  Without the library FK_GATES_BROTLI fails loudly with FK_ERR_UNSUPPORTED; FK_GATES_RAW needs nothing.
 #include "common.hpp"
+#include "r1cs.hpp"
 #include <new>
 #include <stdexcept>
 #include <algorithm>
@@ -868,10 +869,7 @@ void fk_blob_free(fk_blob *b) { delete b; }
 
 }  // extern "C"
 
-// the resident constraint system straight from the decoded stream (spmv.hip); its dictionary and density flags are reused as they are
-namespace fk { int r1cs_load_coded(fk_ctx *ctx, uint32_t num_input, uint32_t num_aux, uint64_t num_gates, const uint64_t *const ptr[3], const uint32_t *const col[3],
-                                   const uint32_t *const cidx[3], const Fr *table, uint64_t n_table, fk_r1cs_dev **out, const uint8_t *const density[3] = nullptr); }
-
+// the resident constraint system straight from the decoded stream (r1cs.hpp: r1cs_load_coded); its dictionary and density flags are reused as they are
 extern "C" int fk_r1cs_load_gates(fk_ctx *ctx, const fk_gates *g, fk_r1cs_dev **out) {
     if (!ctx || !g || !out) return FK_ERR_BAD_ARG;
     return fk_guard(ctx, [&]() -> int {

@@ -16,7 +16,7 @@ struct BinArgs {
 // (inside a group still longest first), so that a rank's rows of a class are one contiguous run per copy; which residue a
 // copy needs depends on the copy (row t = copy * base_gates + row), with period P = W / gcd(base_gates, W) copies.
 struct SliceLists {
-    uint32_t *d_list[3] = {nullptr, nullptr, nullptr};    // per matrix, same length and class boundaries as rowlist
+    DevArr<uint32_t> d_list[3];                           // per matrix, same length and class boundaries as rowlist
     uint32_t cnt[SPMV_SEGS][8] = {{0}}, offs[SPMV_SEGS][8] = {{0}};       // per segment: rows of each residue / their first position in the class
     bool built = false;
 };
@@ -28,27 +28,28 @@ struct SliceArgs {
 };
 }  // namespace fk
 
+// Every device array is a DevArr: deleting the object frees them all (fk_r1cs_free), as does any early return of the loader (spmv_plan.hpp fills the plain fields).
 struct fk_r1cs_dev {
     uint32_t num_input = 0, num_aux = 0;
     uint64_t num_gates = 0;
-    uint64_t *ptr[3] = {nullptr, nullptr, nullptr};
-    uint32_t *col[3] = {nullptr, nullptr, nullptr};
-    uint32_t *cidx[3] = {nullptr, nullptr, nullptr};
-    fk::Fr *table = nullptr;
+    fk::DevArr<uint64_t> ptr[3];
+    fk::DevArr<uint32_t> col[3], cidx[3];
+    fk::DevArr<fk::Fr> table;
     uint64_t n_table = 0, nnz[3] = {0, 0, 0};
-    uint8_t *d_a_aux = nullptr, *d_b_in = nullptr, *d_b_aux = nullptr;
+    fk::DevArr<uint8_t> d_a_aux, d_b_in, d_b_aux;
     uint64_t n_a_aux = 0, n_b_in = 0, n_b_aux = 0;   // popcounts
-    uint32_t *d_idx_a = nullptr, *d_idx_b = nullptr; // variables of the A / B query in query order
+    fk::DevArr<uint32_t> d_idx_a, d_idx_b;           // variables of the A / B query in query order
     fk::QueryIdx qidx;
     // tiled system (fk_r1cs_load_tiled): the CSR above is ONE instance (base_gates rows, base_input / base_aux variables)
     // and stands for `copies` of it; num_input / num_aux / num_gates / nnz are the totals
     uint32_t copies = 1, base_input = 0, base_aux = 0, base_gates = 0;
     // matrices with long rows: the (instance's) rows in classes by length, sorted by length inside a class (see spmv_binned_kernel)
-    uint32_t *rowlist[3] = {nullptr, nullptr, nullptr};
+    fk::DevArr<uint32_t> rowlist[3];
     fk::BinArgs bins;
     // batch circuits of >= 64 copies: the rows of middling length that spmv_tiled_wave_kernel takes (matrix << 30 | row, circuit
     // order) and where they sit in rowlist (sorted by length: [wave_from, wave_to) of each matrix)
-    uint32_t *d_wavelist = nullptr, n_wavelist = 0, wave_from[3] = {0, 0, 0}, wave_to[3] = {0, 0, 0};
+    fk::DevArr<uint32_t> d_wavelist;
+    uint32_t n_wavelist = 0, wave_from[3] = {0, 0, 0}, wave_to[3] = {0, 0, 0};
     // Row windows (explicit systems whose class lists are block-sorted, all three matrices binned): the gate rows cut into win_k runs of
     // consecutive rows.  win_cnt[j][s]: entries of launch segment s whose row lies below win_row[j] (a PREFIX of the segment's list: the
     // lists are ordered by blocks of consecutive rows); win_need[j]: how many leading elements of z the rows below win_row[j + 1] read.
@@ -57,15 +58,16 @@ struct fk_r1cs_dev {
     uint32_t win_k = 0;
     uint64_t win_row[WIN_MAX + 1] = {0}, win_need[WIN_MAX] = {0};
     uint32_t win_cnt[WIN_MAX + 1][fk::SPMV_SEGS] = {{0}};
-    // Repeated linear combinations (explicit systems, found once at load: spmv.hip, alias plan).  Row (dm, drow) of a binned matrix whose
+    // Repeated linear combinations (explicit systems, found once at load: spmv_plan.hpp, alias plan).  Row (dm, drow) of a binned matrix whose
     // columns and coefficient indices are byte-identical to those of an earlier, non-alias row (sm, srow) at most alias_lookback gates
     // back is an ALIAS: the unsliced evaluation leaves it out of the class lists (the dedup set: rowlist_dd / bins_dd / win_cnt_dd, the
     // same class and block order as rowlist / bins / win_cnt) and spmv_alias_kernel copies out[sm][srow] to out[dm][drow] behind it.
     // d_alias: drow | (drow - srow) << 32 | dm << 48 | sm << 50, sorted by (drow, dm); win_alias[j]: aliases whose drow < win_row[j].
     // The sliced and the tiled evaluations and h_rowlist keep the full lists.
-    uint64_t *d_alias = nullptr, n_alias = 0, alias_terms = 0;
+    fk::DevArr<uint64_t> d_alias;
+    uint64_t n_alias = 0, alias_terms = 0;
     uint32_t alias_min = 0, alias_lookback = 0;
-    uint32_t *rowlist_dd[3] = {nullptr, nullptr, nullptr};       // only for the matrices that have aliases; bins_dd points at rowlist for the others
+    fk::DevArr<uint32_t> rowlist_dd[3];              // only for the matrices that have aliases; bins_dd points at rowlist for the others
     fk::BinArgs bins_dd;
     uint32_t win_cnt_dd[WIN_MAX + 1][fk::SPMV_SEGS] = {{0}};
     uint64_t win_alias[WIN_MAX + 1] = {0};
@@ -106,6 +108,8 @@ static inline int key_delta_ok(fk_ctx *ctx, const fk_key *key) {
     return FK_OK;
 }
 // spmv.hip
+int r1cs_load_coded(fk_ctx *ctx, uint32_t num_input, uint32_t num_aux, uint64_t num_gates, const uint64_t *const ptr[3], const uint32_t *const col[3],
+                    const uint32_t *const cidx[3], const Fr *table, uint64_t n_table, fk_r1cs_dev **out, const uint8_t *const density[3] = nullptr);
 int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a, void *d_b, void *d_c, bool sliced, uint32_t rank, uint32_t log_w, uint64_t n_out, int window);
 int prove_r1cs_dev_impl(fk_ctx *ctx, const fk_key *key, const fk_r1cs_dev *r, const void *d_z, const uint64_t rr[4], const uint64_t ss[4],
                         uint8_t out_proof[FK_PROOF_BYTES], fk_timings *tm, const std::function<int()> *after_eval, const std::function<int()> *before_block);

@@ -15,15 +15,10 @@
 // stays in L2.  Index 0 is reserved for ONE (multiply skipped, exactly as bellman's eval does).
 // Kernel: one lane per (matrix, row); HBM-bound gather of z (32 B per term).
 #include "common.hpp"
-#include <string.h>
-#include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <thread>
-#include <unordered_map>
-#include <string>
+#include <memory>
 
-#include "r1cs.hpp"
+#include "spmv_plan.hpp"
 #include "../../include/fawkes_hip_inspect.h"
 
 namespace fk {
@@ -223,10 +218,93 @@ __global__ __launch_bounds__(256) void spmv_alias_kernel(Fr *out0, Fr *out1, Fr 
     dst[drow] = src[srow];
 }
 
-// FK_SPMV_DEDUP=0 (a run-time switch, read once): no alias plan at load, the full class lists and no alias kernel in the evaluation
-static bool spmv_dedup_on() {
-    static const bool on = !(getenv("FK_SPMV_DEDUP") && atoi(getenv("FK_SPMV_DEDUP")) == 0);
-    return on;
+// one host array into an exactly-sized device array of its own (pad: elements allocated behind the n copied)
+template <class T>
+static int dev_upload(fk_ctx *ctx, DevArr<T> &d, const T *h, size_t n, size_t pad = 0) {
+    if (d.alloc(n + pad) != hipSuccess) FK_SET_ERR(ctx, FK_ERR_OOM, "r1cs: device allocation failed");
+    if (n && hipMemcpy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) FK_SET_ERR(ctx, FK_ERR_HIP, "r1cs: upload failed");
+    return FK_OK;
+}
+
+// win_need of the row windows the plan cut (r1cs.hpp), from the uploaded columns: a host pass over 10^9 columns is what the kernel avoids
+static int window_need(fk_ctx *ctx, const SpmvPlan &p, fk_r1cs_dev &r) {
+    const uint32_t K = r.win_k;
+    if (!K) return FK_OK;
+    DevArr<uint32_t> d_mx;
+    if (d_mx.alloc(K) != hipSuccess || hipMemset(d_mx, 0, K * 4) != hipSuccess) FK_SET_ERR(ctx, FK_ERR_OOM, "r1cs: device allocation failed");
+    for (int k = 0; k < 3; k++) {
+        WinBounds wb{}; wb.k = K;
+        for (uint32_t j = 0; j <= K; j++) wb.tb[j] = p.ptr[k][r.win_row[j]];
+        if (wb.tb[K]) hipLaunchKernelGGL(col_window_max_kernel, dim3(2048), dim3(256), 0, ctx->stream, r.col[k].p, wb, d_mx.p);
+    }
+    uint32_t mx[fk_r1cs_dev::WIN_MAX] = {0};
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(mx, d_mx, K * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        FK_SET_ERR(ctx, FK_ERR_HIP, "r1cs: window planning failed");
+    uint64_t run = p.num_input;                          // the rows behind the gates (input_i * 0 = 0) read the inputs: part of the first piece
+    for (uint32_t j = 0; j < K; j++) { run = std::max<uint64_t>(run, (uint64_t)mx[j] + 1); r.win_need[j] = j + 1 == K ? (uint64_t)p.num_input + p.num_aux : run; }
+    return FK_OK;
+}
+
+// The loader: the plan's stages (spmv_plan.hpp) in their order, each followed by the upload of what it left; win_need and the A query's
+// fingerprint come from the device.  The resident object owns every device array, so whatever ends the load early frees what was built.
+static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1cs_dev **out, const uint32_t *const *pre_cidx = nullptr,
+                          const Fr *pre_table = nullptr, uint64_t n_pre_table = 0, const uint8_t *const *pre_density = nullptr) {
+    if (!ctx || !cs || !out) return FK_ERR_BAD_ARG;
+    *out = nullptr;
+    SpmvPlan p(cs, copies, pre_cidx, pre_table, n_pre_table, pre_density, ctx->err);
+    std::unique_ptr<fk_r1cs_dev> r(new fk_r1cs_dev());
+    auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    FK_TRY(plan_validate(p, *r));
+    FK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto t_load0 = std::chrono::steady_clock::now();
+    double t_copy = 0;
+    FK_TRY(plan_class_lists(p, *r));
+    for (int k = 0; k < 3; k++) {
+        FK_TRY(plan_coefficients(p, *r, k));
+        const uint64_t nnz = p.ptr[k][p.ng];
+        const auto tc0 = std::chrono::steady_clock::now();
+        FK_TRY(dev_upload(ctx, r->ptr[k], p.ptr[k], p.ng + 1));
+        FK_TRY(dev_upload(ctx, r->col[k], p.col[k], nnz, 1));
+        FK_TRY(dev_upload(ctx, r->cidx[k], p.trusted() ? pre_cidx[k] : p.cidx[k].data(), nnz, 1));
+        t_copy += since(tc0);
+        if (pre_cidx || !p.want_alias) std::vector<uint32_t>().swap(p.cidx[k]);
+        if (!r->h_rowlist[k].empty()) FK_TRY(dev_upload(ctx, r->rowlist[k], r->h_rowlist[k].data(), r->h_rowlist[k].size()));
+        r->bins.rowlist[k] = r->rowlist[k];
+    }
+    if (getenv("FK_GATES_TRACE")) fprintf(stderr, "[fk] r1cs load: %.2f s so far, %.2f of them allocating and copying the matrices\n", since(t_load0), t_copy);
+    plan_windows(p, *r);
+    FK_TRY(window_need(ctx, p, *r));
+    FK_TRY(plan_aliases(p, *r));
+    FK_TRY(plan_dedup(p, *r));
+    for (int k = 0; k < 3 && r->n_alias; k++) {       // bins_dd points at the full list of a matrix that has no alias
+        if (!p.is_alias[k].empty()) FK_TRY(dev_upload(ctx, r->rowlist_dd[k], p.dd[k].data(), p.dd[k].size(), 1));
+        r->bins_dd.rowlist[k] = p.is_alias[k].empty() ? r->rowlist[k].p : r->rowlist_dd[k].p;
+    }
+    if (r->n_alias) FK_TRY(dev_upload(ctx, r->d_alias, p.alias.data(), p.alias.size()));
+    std::vector<uint64_t>().swap(p.alias); for (int k = 0; k < 3; k++) { std::vector<uint32_t>().swap(p.dd[k]); std::vector<uint8_t>().swap(p.is_alias[k]); }
+    if (getenv("FK_GATES_TRACE") && p.want_alias && r->bins.mask) fprintf(stderr, "[fk] r1cs load: %.2f s so far, alias plan done (%llu aliases for %llu terms)\n", since(t_load0),
+                                                         (unsigned long long)r->n_alias, (unsigned long long)r->alias_terms);
+    plan_wavelist(p, *r);
+    if (r->n_wavelist) FK_TRY(dev_upload(ctx, r->d_wavelist, p.wavelist.data(), p.wavelist.size()));
+    plan_queries(p, *r);
+    FK_TRY(dev_upload(ctx, r->table, p.table.data(), p.table.size()));
+    for (auto m : {std::make_pair(&r->d_a_aux, &p.a_aux), std::make_pair(&r->d_b_in, &p.b_in), std::make_pair(&r->d_b_aux, &p.b_aux)}) FK_TRY(dev_upload(ctx, *m.first, m.second->data(), m.second->size()));
+    FK_TRY(dev_upload(ctx, r->d_idx_a, p.idx_a.data(), p.idx_a.size(), 1));
+    FK_TRY(dev_upload(ctx, r->d_idx_b, p.idx_b.data(), p.idx_b.size(), 1));
+    r->qidx.a = r->d_idx_a; r->qidx.b = r->d_idx_b; r->qidx.n_a = p.idx_a.size(); r->qidx.n_b = p.idx_b.size();
+    // what a key's padded A array (msm.hip: key_a_pad) is cached under: which aux variables the A query takes
+    FK_TRY(query_fingerprint(ctx, r->d_idx_a, p.idx_a.size(), &r->qidx.a_fp));
+    r->qidx.a_fp_valid = true;
+    *out = r.release();
+    return FK_OK;
+}
+
+int r1cs_load_coded(fk_ctx *ctx, uint32_t num_input, uint32_t num_aux, uint64_t num_gates, const uint64_t *const ptr[3], const uint32_t *const col[3],
+                    const uint32_t *const cidx[3], const Fr *table, uint64_t n_table, fk_r1cs_dev **out, const uint8_t *const density[3]) {
+    fk_r1cs cs{};
+    cs.num_input = num_input; cs.num_aux = num_aux; cs.num_gates = num_gates;
+    cs.a_ptr = ptr[0]; cs.a_col = col[0]; cs.b_ptr = ptr[1]; cs.b_col = col[1]; cs.c_ptr = ptr[2]; cs.c_col = col[2];
+    return r1cs_load_impl(ctx, &cs, 1, out, cidx, table, n_table, density);
 }
 
 }  // namespace fk
@@ -238,436 +316,10 @@ extern "C" {
 void fk_r1cs_free(fk_ctx *ctx, fk_r1cs_dev *r) {
     if (!r) return;
     if (ctx) (void)hipSetDevice(ctx->device);
-    for (int k = 0; k < 3; k++) { if (r->ptr[k]) (void)hipFree(r->ptr[k]); if (r->col[k]) (void)hipFree(r->col[k]); if (r->cidx[k]) (void)hipFree(r->cidx[k]); if (r->rowlist[k]) (void)hipFree(r->rowlist[k]); }
-    for (void *p : {(void *)r->table, (void *)r->d_a_aux, (void *)r->d_b_in, (void *)r->d_b_aux, (void *)r->d_idx_a, (void *)r->d_idx_b}) if (p) (void)hipFree(p);
-    for (auto &sl : r->slices) for (uint32_t *p : sl.d_list) if (p) (void)hipFree(p);
-    if (r->d_wavelist) (void)hipFree(r->d_wavelist);
-    for (uint32_t *p : r->rowlist_dd) if (p) (void)hipFree(p);
-    if (r->d_alias) (void)hipFree(r->d_alias);
     delete r;
 }
 
-// cs: one instance; the resident system stands for `copies` of it (1 = the system itself).  pre_cidx / pre_table: the
-// coefficients already dictionary-coded (gatestream.hip: slot 0 = ONE), cs->*_val then unused.
-// pre_density: a_aux / b_in / b_aux flags the caller already derived (the gate decoder does, while it parses): the arrays then come
-// from this library's own decoder, which has range-checked every index -- the per-term passes over the host arrays are skipped.
-static int r1cs_load_impl(fk_ctx *ctx, const fk_r1cs *cs, uint32_t copies, fk_r1cs_dev **out, const uint32_t *const *pre_cidx = nullptr,
-                          const Fr *pre_table = nullptr, uint64_t n_pre_table = 0, const uint8_t *const *pre_density = nullptr) {
-    if (!ctx || !cs || !out) return FK_ERR_BAD_ARG;
-    *out = nullptr;
-    if (copies == 0) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: copies must be at least 1");
-    FK_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t *ptrs[3] = {cs->a_ptr, cs->b_ptr, cs->c_ptr};
-    const uint32_t *cols[3] = {cs->a_col, cs->b_col, cs->c_col};
-    const uint64_t *vals[3] = {cs->a_val, cs->b_val, cs->c_val};
-    const uint64_t nv = (uint64_t)cs->num_input + cs->num_aux;
-    if (cs->num_input == 0) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: num_input must include the constant ONE");
-    for (int k = 0; k < 3; k++) {
-        if (!ptrs[k]) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: null row pointer");
-        if (ptrs[k][0] != 0) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: row_ptr[0] must be 0");
-        if (pre_density && pre_cidx) continue;
-        for (uint64_t g = 0; g < cs->num_gates; g++) if (ptrs[k][g + 1] < ptrs[k][g]) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: row_ptr not monotone");
-        const uint64_t nnz = ptrs[k][cs->num_gates];
-        if (nnz && !cols[k]) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: null column array");   // vals[k] == NULL: all coefficients ONE
-        for (uint64_t i = 0; i < nnz; i++) if (cols[k][i] >= nv) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: variable index %u out of range", cols[k][i]);
-    }
-    // totals of the tiled system: ONE is shared, inputs and aux variables are per copy
-    const uint64_t t_in = 1 + (uint64_t)copies * (cs->num_input - 1), t_aux = (uint64_t)copies * cs->num_aux, t_gates = (uint64_t)copies * cs->num_gates;
-    if (t_in + t_aux > 0xffffffffull || t_gates + t_in > 0xffffffffull || (copies > 1 && cs->num_gates == 0))
-        FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: %u copies of this system do not fit 32-bit variable / row indices", copies);
-    const auto t_load0 = std::chrono::steady_clock::now();
-    double t_copy = 0;
-    fk_r1cs_dev *r = new fk_r1cs_dev();
-    r->num_input = (uint32_t)t_in; r->num_aux = (uint32_t)t_aux; r->num_gates = t_gates;
-    r->copies = copies; r->base_input = cs->num_input; r->base_aux = cs->num_aux; r->base_gates = (uint32_t)cs->num_gates;
-    // coefficient dictionary; slot 0 = ONE
-    std::unordered_map<std::string, uint32_t> dict;
-    std::vector<Fr> table;
-    const Fr one = Fr::one();
-    table.push_back(one);
-    dict.emplace(std::string((const char *)&one, 32), 0u);
-    if (pre_cidx) {
-        if (!pre_table || !n_pre_table || pre_table[0] != one) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: coefficient table must start with ONE");
-        table.assign(pre_table, pre_table + n_pre_table);
-    }
-    std::vector<uint8_t> a_aux(cs->num_aux ? cs->num_aux : 1, 0), b_in(cs->num_input, 0), b_aux(cs->num_aux ? cs->num_aux : 1, 0);
-    const bool trusted = pre_density && pre_cidx;
-    if (trusted) {
-        if (cs->num_aux) { memcpy(a_aux.data(), pre_density[0], cs->num_aux); memcpy(b_aux.data(), pre_density[2], cs->num_aux); }
-        memcpy(b_in.data(), pre_density[1], cs->num_input);
-    }
-    int rc = FK_OK;
-    auto fail = [&](int code) { fk_r1cs_free(ctx, r); return code; };
-    // rows of [wave_lo, wave_hi) terms of a batch of >= wave_copies copies go to spmv_tiled_wave_kernel (see there).  The length
-    // classes are 16 lanes per row from 64 terms, 8 from 32, 4 from 16, 2 from 8, one lane below; with [4, 64) the wave kernel takes
-    // the WHOLE 8-, 4- and 2-lane classes and the head (4 .. 7 terms) of the one-lane class.  The clipping in r1cs_eval_impl removes a
-    // prefix or a suffix of a class segment, so the range may cut only the first class (wave_hi >= 64) and the last one (wave_lo < 8):
-    // an upper bound strictly inside a middle class is snapped down to that class's boundary (experiment builds can set any value).
-    static const uint32_t wave_copies = (uint32_t)tune("FK_SPMV_WAVE_MIN_COPIES", 64), wave_lo = 4;
-    static const uint32_t wave_hi = [] {
-        const uint32_t v = (uint32_t)std::min(1024, std::max(32, tune("FK_SPMV_WAVE_HI", 64)));
-        return v >= 64 ? v : 32u;           // 32 .. 63 -> 32: the boundary between the 8-lane and the 4-lane class
-    }();
-    uint64_t bin_min = 8;          // rows this long make a matrix binned; FK_SPMV_BIN_MIN=0 turns the binned product off (a run-time switch: the tests run both kernels)
-    if (const char *e = getenv("FK_SPMV_BIN_MIN")) { bin_min = strtoull(e, nullptr, 10); if (!bin_min) bin_min = ~0ull; }
-    // The class lists of a matrix depend on its row lengths alone: the three are built side by side (a third of a second each for the
-    // benchmark's 33.5 M rows) before the matrices are uploaded.
-    struct ListPlan { bool binned = false; std::vector<uint32_t> list; uint32_t cls_n[SPMV_CLASSES] = {0}, wave_from = 0, wave_to = 0; };
-    ListPlan plans[3];
-    static const uint32_t cls_lo[SPMV_CLASSES] = {64, 32, 16, 8, 0}, cls_lg[SPMV_CLASSES] = {4, 3, 2, 1, 0};
-    auto build_lists = [&](int k) {
-        ListPlan &lp = plans[k];
-        uint64_t maxlen = 0;
-        for (uint64_t g = 0; g < cs->num_gates; g++) if (ptrs[k][g + 1] - ptrs[k][g] > maxlen) maxlen = ptrs[k][g + 1] - ptrs[k][g];
-        if (!(maxlen >= bin_min && cs->num_gates && cs->num_gates < 0xffffffffull)) return;
-        lp.binned = true;
-        const uint32_t ng = (uint32_t)cs->num_gates, CAP = 1024;            // counting sort by min(length, CAP), descending, stable
-        std::vector<uint32_t> cnt(CAP + 2, 0);
-        std::vector<uint32_t> &list = lp.list;
-        list.resize(ng);
-        auto key = [&](uint32_t g) { const uint64_t l = ptrs[k][g + 1] - ptrs[k][g]; return (uint32_t)(l < CAP ? l : CAP); };
-        for (uint32_t g = 0; g < ng; g++) cnt[CAP - key(g) + 1]++;
-        for (uint32_t i = 0; i <= CAP; i++) cnt[i + 1] += cnt[i];
-        for (uint32_t g = 0; g < ng; g++) list[cnt[CAP - key(g)]++] = g;
-        // classes: 16 lanes per row from 64 terms, 8 from 32, 4 from 16, 2 from 8, one lane below -- a lane then has 4 .. 7 terms
-        // (one or two four-term steps with a shared reduction) in every class but the last; cnt[i] is now the END of key CAP - i
-        uint32_t cls_start[SPMV_CLASSES];
-        for (int c = 0; c < SPMV_CLASSES; c++) {
-            cls_start[c] = c ? cnt[CAP - cls_lo[c - 1]] : 0;
-            lp.cls_n[c] = (cls_lo[c] ? cnt[CAP - cls_lo[c]] : ng) - cls_start[c];
-        }
-        // A large flat system (a circuit as it comes out of a Parameters file): sorting a class by length over the WHOLE system
-        // puts rows from everywhere in the circuit side by side -- every wave then gathers z from all over the witness and
-        // streams its matrix entries from all over the CSR.  Sort by length inside blocks of consecutive rows instead: the rows
-        // that share a wave still have (nearly) the same length, and what runs at one time reads one window of the circuit
-        // (the benchmark's system with every term explicit: evaluation 15.2 -> see profiles/r03_spmv_rollup_probe.log).
-        static const uint32_t block_rows = (uint32_t)std::max(0, tune("FK_SPMV_BLOCK_ROWS", 4096));
-        if (copies == 1 && block_rows && ng >= 16 * block_rows) {
-            uint32_t pos[SPMV_CLASSES];                            // class c holds the rows of cls_lo[c] <= length < cls_lo[c - 1]
-            for (int c = 0; c < SPMV_CLASSES; c++) pos[c] = cls_start[c];
-            std::vector<uint32_t> bc(CAP + 2);
-            std::vector<uint32_t> tmp(block_rows);
-            for (uint32_t g0 = 0; g0 < ng; g0 += block_rows) {
-                const uint32_t g1 = std::min(ng, g0 + block_rows);
-                std::fill(bc.begin(), bc.end(), 0u);
-                for (uint32_t g = g0; g < g1; g++) bc[CAP - key(g) + 1]++;
-                for (uint32_t i = 0; i <= CAP; i++) bc[i + 1] += bc[i];
-                for (uint32_t g = g0; g < g1; g++) tmp[bc[CAP - key(g)]++] = g;           // the block's rows, longest first (stable)
-                for (uint32_t i = 0; i < g1 - g0; i++) {
-                    const uint32_t l = key(tmp[i]);
-                    int c = 0;
-                    while (l < cls_lo[c]) c++;
-                    list[pos[c]++] = tmp[i];
-                }
-            }
-        }
-        lp.wave_from = cnt[CAP - wave_hi]; lp.wave_to = cnt[CAP - wave_lo];
-    };
-    if (cs->num_gates >= ((uint64_t)1 << 20)) {
-        std::atomic<bool> threw{false};
-        auto guarded = [&](int k) { try { build_lists(k); } catch (...) { threw = true; } };       // (an exception must not leave a thread)
-        {
-            std::thread t1([&] { guarded(1); });
-            std::thread t2;
-            try { t2 = std::thread([&] { guarded(2); }); } catch (...) { guarded(2); }
-            guarded(0);
-            t1.join(); if (t2.joinable()) t2.join();
-        }
-        if (threw) { ctx->err = "r1cs: out of host memory while ordering the rows"; return fail(FK_ERR_OOM); }
-    } else for (int k = 0; k < 3; k++) build_lists(k);
-    const bool want_alias = copies == 1 && spmv_dedup_on();     // the alias plan below reads the coefficient indices of all three matrices
-    std::vector<uint32_t> cidx_keep[3];
-    for (int k = 0; k < 3 && rc == FK_OK; k++) {
-        const uint64_t nnz = ptrs[k][cs->num_gates];
-        r->nnz[k] = nnz * copies;
-        std::vector<uint32_t> &cidx = cidx_keep[k];
-        cidx.resize(trusted ? 1 : nnz ? nnz : 1);
-        Fr last = one; uint32_t last_idx = 0;        // one-entry cache in front of the hash map
-        for (uint64_t i = 0; i < nnz && !trusted; i++) {
-            uint32_t ci = 0;
-            if (pre_cidx) {
-                ci = pre_cidx[k][i];
-                if (ci >= n_pre_table) { ctx->err = "r1cs: coefficient index out of range"; return fail(FK_ERR_BAD_ARG); }
-            } else if (vals[k] && memcmp(vals[k] + 4 * i, &one, 32) != 0) {
-                if (memcmp(vals[k] + 4 * i, &last, 32) == 0) ci = last_idx;
-                else {
-                    std::string key((const char *)(vals[k] + 4 * i), 32);
-                    auto it = dict.find(key);
-                    if (it == dict.end()) {
-                        if (table.size() >= 0xffffffffull) { ctx->err = "r1cs: too many distinct coefficients"; return fail(FK_ERR_BAD_ARG); }
-                        Fr v; memcpy(&v, vals[k] + 4 * i, 32);
-                        it = dict.emplace(key, (uint32_t)table.size()).first;
-                        table.push_back(v);
-                    }
-                    ci = it->second; memcpy(&last, vals[k] + 4 * i, 32); last_idx = ci;
-                }
-            }
-            cidx[i] = ci;
-            const uint32_t v = cols[k][i];
-            if (k == 0) { if (v >= cs->num_input) a_aux[v - cs->num_input] = 1; }
-            else if (k == 1) { if (v < cs->num_input) b_in[v] = 1; else b_aux[v - cs->num_input] = 1; }
-        }
-        const auto tc0 = std::chrono::steady_clock::now();
-        if (hipMalloc((void **)&r->ptr[k], (cs->num_gates + 1) * 8) != hipSuccess || hipMalloc((void **)&r->col[k], (nnz + 1) * 4) != hipSuccess ||
-            hipMalloc((void **)&r->cidx[k], (nnz + 1) * 4) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
-        if (hipMemcpy(r->ptr[k], ptrs[k], (cs->num_gates + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) rc = FK_ERR_HIP;
-        if (nnz && hipMemcpy(r->col[k], cols[k], nnz * 4, hipMemcpyHostToDevice) != hipSuccess) rc = FK_ERR_HIP;
-        if (nnz && hipMemcpy(r->cidx[k], trusted ? pre_cidx[k] : cidx.data(), nnz * 4, hipMemcpyHostToDevice) != hipSuccess) rc = FK_ERR_HIP;
-        t_copy += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count();
-        if (pre_cidx || !want_alias) std::vector<uint32_t>().swap(cidx);
-        // length classes (spmv_binned_kernel) when the matrix has long rows: planned above (build_lists)
-        ListPlan &lp = plans[k];
-        if (lp.binned && rc == FK_OK) {
-            const uint32_t ng = (uint32_t)cs->num_gates;
-            std::vector<uint32_t> &list = lp.list;
-            const uint32_t *cls_n = lp.cls_n;
-            r->wave_from[k] = lp.wave_from; r->wave_to[k] = lp.wave_to;             // rows of wave_lo <= length < wave_hi
-            if (hipMalloc((void **)&r->rowlist[k], (size_t)ng * 4) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
-            if (hipMemcpy(r->rowlist[k], list.data(), (size_t)ng * 4, hipMemcpyHostToDevice) != hipSuccess) rc = FK_ERR_HIP;
-            r->h_rowlist[k] = std::move(list);
-            BinArgs &b = r->bins;
-            b.rowlist[k] = r->rowlist[k]; b.mask |= 1u << k;
-            uint32_t off = 0;
-            for (int c = 0; c < SPMV_CLASSES; c++) {
-                if (cls_n[c]) {
-                    const uint64_t groups = (uint64_t)cls_n[c] * copies, per = 256u >> cls_lg[c], blocks = (groups + per - 1) / per;
-                    if (b.first_block[b.nseg] + blocks > 0x7fffffffull) { ctx->err = "r1cs: system too large for the binned product"; return fail(FK_ERR_BAD_ARG); }
-                    b.lg[b.nseg] = cls_lg[c]; b.mtx[b.nseg] = k; b.n_rows[b.nseg] = cls_n[c]; b.list_off[b.nseg] = off;
-                    b.first_block[b.nseg + 1] = b.first_block[b.nseg] + (uint32_t)blocks;
-                    b.nseg++;
-                }
-                off += cls_n[c];
-            }
-        }
-    }
-    if (getenv("FK_GATES_TRACE")) fprintf(stderr, "[fk] r1cs load: %.2f s so far, %.2f of them allocating and copying the matrices\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_load0).count(), t_copy);
-    if (rc != FK_OK) { ctx->err = "r1cs: upload failed"; return fail(rc); }
-    // row windows for the chunked hand-over of fk_prove_r1cs (r1cs.hpp): explicit systems with block-sorted class lists, every matrix binned
-    {
-        static const uint32_t block_rows_w = (uint32_t)std::max(0, tune("FK_SPMV_BLOCK_ROWS", 4096));
-        static const int t_win = std::min<int>(fk_r1cs_dev::WIN_MAX, std::max(0, tune("FK_SPMV_WINDOWS", 8)));
-        const uint64_t ng = cs->num_gates;
-        if (copies == 1 && t_win >= 2 && block_rows_w && ng >= 16ull * block_rows_w && ng < 0xffffffffull && r->bins.mask == 7u) {
-            const uint32_t K = (uint32_t)t_win;
-            for (uint32_t j = 0; j <= K; j++) r->win_row[j] = j == K ? ng : (ng * j / K) / block_rows_w * block_rows_w;
-            for (uint32_t s = 0; s < r->bins.nseg; s++) {
-                const std::vector<uint32_t> &lst = r->h_rowlist[r->bins.mtx[s]];
-                const uint32_t *lo = lst.data() + r->bins.list_off[s], *hi = lo + r->bins.n_rows[s];
-                for (uint32_t j = 0; j <= K; j++) {
-                    const uint64_t bound = r->win_row[j];
-                    r->win_cnt[j][s] = (uint32_t)(std::partition_point(lo, hi, [&](uint32_t row) { return row < bound; }) - lo);       // a prefix: blocks of rows ascend inside a class
-                }
-            }
-            uint32_t *d_mx = nullptr;
-            if (hipMalloc((void **)&d_mx, K * 4) != hipSuccess || hipMemset(d_mx, 0, K * 4) != hipSuccess) { if (d_mx) (void)hipFree(d_mx); ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
-            for (int k = 0; k < 3; k++) {
-                WinBounds wb{}; wb.k = K;
-                for (uint32_t j = 0; j <= K; j++) wb.tb[j] = ptrs[k][r->win_row[j]];
-                if (wb.tb[K]) hipLaunchKernelGGL(col_window_max_kernel, dim3(2048), dim3(256), 0, ctx->stream, r->col[k], wb, d_mx);
-            }
-            uint32_t mx[fk_r1cs_dev::WIN_MAX] = {0};
-            const bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpy(mx, d_mx, K * 4, hipMemcpyDeviceToHost) == hipSuccess;
-            (void)hipFree(d_mx);
-            if (!ok) { ctx->err = "r1cs: window planning failed"; return fail(FK_ERR_HIP); }
-            uint64_t run = cs->num_input;                          // the rows behind the gates (input_i * 0 = 0) read the inputs: part of the first piece
-            for (uint32_t j = 0; j < K; j++) { run = std::max<uint64_t>(run, (uint64_t)mx[j] + 1); r->win_need[j] = j + 1 == K ? nv : run; }
-            r->win_k = K;
-        }
-    }
-    // Alias plan: circuits repeat linear combinations (the Poseidon S-box multiplies a lazily expanded combination by itself: the B row of a
-    // gate equals its A row, or the A row two gates back) -- 29.6 % of the benchmark transaction's terms sit in such rows.  Which rows repeat is
-    // a property of the system, not of the witness, and out[dst] = out[src] holds for any z: found once here, see r1cs.hpp.  Gates in row
-    // order, matrices A, B, C inside a gate; a row of >= dd_min terms is an alias of the EARLIEST row, at most dd_back gates back, that has the
-    // same columns and coefficient indices (memcmp; the hash only finds candidates) and is not an alias itself.  Rows of a matrix that is not
-    // binned are sources only.  The bounded look-back makes it one streaming pass with O(dd_back) state, and src row <= dst row.
-    static const uint32_t dd_min = (uint32_t)std::max(1, tune("FK_SPMV_DEDUP_MIN", 4)), dd_back = (uint32_t)std::min(4096, std::max(0, tune("FK_SPMV_DEDUP_LOOKBACK", 8)));
-    r->alias_min = dd_min; r->alias_lookback = dd_back;
-    if (want_alias && r->bins.mask && cs->num_gates && cs->num_gates < 0xffffffffull) {
-        const uint64_t ng = cs->num_gates, NONE = ~0ull;
-        const uint32_t *h_cidx[3];
-        for (int k = 0; k < 3; k++) h_cidx[k] = pre_cidx ? pre_cidx[k] : cidx_keep[k].data();
-        // pass 1 (threads over blocks of gates, each reading dd_back gates into the block before it): the NEAREST earlier identical row of
-        // every row that has one -- independent of which rows end up as aliases.  key = gate * 3 + matrix.
-        struct Cand { uint64_t key, prev; };
-        auto scan = [&](uint64_t g0, uint64_t g1, std::vector<Cand> &found) {
-            const uint64_t R = (uint64_t)dd_back + 1;
-            std::vector<uint64_t> hs(R * 3), ln(R * 3, 0);              // ring over the last R gates; ln = 0: shorter than dd_min
-            for (uint64_t g = g0 > dd_back ? g0 - dd_back : 0; g < g1; g++) {
-                const size_t slot = (size_t)(g % R) * 3;
-                for (int k = 0; k < 3; k++) {
-                    const uint64_t lo = ptrs[k][g], len = ptrs[k][g + 1] - lo;
-                    ln[slot + k] = 0;
-                    if (len < dd_min) continue;
-                    uint64_t h = len;
-                    for (uint64_t i = 0; i < len; i++) h = (h ^ (cols[k][lo + i] | (uint64_t)h_cidx[k][lo + i] << 32)) * 0x9e3779b97f4a7c15ull + (h >> 31);
-                    hs[slot + k] = h; ln[slot + k] = len;
-                    if (g < g0) continue;
-                    auto same = [&](uint64_t g2, int k2) {
-                        const size_t s2 = (size_t)(g2 % R) * 3 + k2;
-                        if (ln[s2] != len || hs[s2] != h) return false;
-                        const uint64_t lo2 = ptrs[k2][g2];
-                        return memcmp(cols[k2] + lo2, cols[k] + lo, len * 4) == 0 && memcmp(h_cidx[k2] + lo2, h_cidx[k] + lo, len * 4) == 0;
-                    };
-                    uint64_t prev = NONE;
-                    for (int k2 = k - 1; k2 >= 0 && prev == NONE; k2--) if (same(g, k2)) prev = g * 3 + k2;
-                    for (uint64_t d = 1; d <= dd_back && d <= g && prev == NONE; d++)
-                        for (int k2 = 2; k2 >= 0 && prev == NONE; k2--) if (same(g - d, k2)) prev = (g - d) * 3 + k2;
-                    if (prev != NONE) found.push_back({g * 3 + k, prev});
-                }
-            }
-        };
-        const uint32_t n_thr = ng >= ((uint64_t)1 << 20) ? std::min(16u, std::max(1u, host_threads())) : 1u;
-        std::vector<std::vector<Cand>> found(n_thr);
-        std::vector<uint64_t> alias;                 // the device table's entries, in (dst row, dst matrix) order
-        std::vector<uint8_t> is_alias[3];
-        try {
-            std::atomic<bool> threw{false};
-            auto guarded = [&](uint32_t t) { try { scan(ng * t / n_thr, ng * (t + 1) / n_thr, found[t]); } catch (...) { threw = true; } };
-            {
-                std::vector<std::thread> pool;
-                for (uint32_t t = 1; t < n_thr; t++) { try { pool.emplace_back(guarded, t); } catch (...) { guarded(t); } }
-                guarded(0);
-                for (auto &th : pool) th.join();
-            }
-            if (threw) throw std::bad_alloc();
-            // pass 2 (serial, over the rows that have an identical predecessor only): walk the chain of identical rows back through the
-            // look-back and take the earliest one that is not an alias
-            struct Seen { uint64_t key, prev; bool alias; };
-            const uint64_t RS = 3 * ((uint64_t)dd_back + 1);
-            std::vector<Seen> ring(RS, Seen{NONE, NONE, false});
-            for (uint32_t t = 0; t < n_thr; t++) {
-                for (const Cand &c : found[t]) {
-                    const uint64_t g = c.key / 3; const uint32_t dm = (uint32_t)(c.key % 3);
-                    Seen &me = ring[c.key % RS];
-                    me = Seen{c.key, c.prev, false};
-                    if (!((r->bins.mask >> dm) & 1)) continue;
-                    uint64_t best = NONE;
-                    for (uint64_t cur = c.prev; cur != NONE && g - cur / 3 <= dd_back;) {
-                        const Seen &e = ring[cur % RS];
-                        const bool known = e.key == cur;         // not known: the row has no identical predecessor in ITS look-back, it is a source
-                        if (!known || !e.alias) best = cur;
-                        cur = known ? e.prev : NONE;
-                    }
-                    if (best == NONE) continue;
-                    me.alias = true;
-                    const uint64_t sg = best / 3, sm = best % 3;
-                    if (is_alias[dm].empty()) is_alias[dm].assign(ng, 0);
-                    is_alias[dm][g] = 1;
-                    alias.push_back(g | (g - sg) << 32 | (uint64_t)dm << 48 | sm << 50);
-                    r->alias_terms += ptrs[dm][g + 1] - ptrs[dm][g];
-                }
-                std::vector<Cand>().swap(found[t]);
-            }
-        } catch (...) { ctx->err = "r1cs: out of host memory while looking for repeated rows"; return fail(FK_ERR_OOM); }
-        if (!alias.empty()) {
-            // the dedup set: the class lists without the alias rows -- same class order, same block order, hence the same window prefixes
-            BinArgs &d = r->bins_dd;
-            d.mask = r->bins.mask;
-            std::vector<uint32_t> dd[3];
-            for (uint32_t s = 0; s < r->bins.nseg; s++) {
-                const uint32_t k = r->bins.mtx[s], nr = r->bins.n_rows[s];
-                const uint32_t *src = r->h_rowlist[k].data() + r->bins.list_off[s];
-                uint32_t off = r->bins.list_off[s], kept = nr;
-                const uint32_t *lo = src;
-                if (!is_alias[k].empty()) {
-                    off = (uint32_t)dd[k].size();
-                    for (uint32_t i = 0; i < nr; i++) if (!is_alias[k][src[i]]) dd[k].push_back(src[i]);
-                    kept = (uint32_t)dd[k].size() - off;
-                }
-                if (!kept) continue;
-                const uint32_t sd = d.nseg++;
-                const uint64_t per = 256u >> r->bins.lg[s];
-                d.lg[sd] = r->bins.lg[s]; d.mtx[sd] = k; d.n_rows[sd] = kept; d.list_off[sd] = off;
-                d.first_block[sd + 1] = d.first_block[sd] + (uint32_t)((kept + per - 1) / per);
-                if (!is_alias[k].empty()) lo = dd[k].data() + off;          // (dd[k] grows no more inside this iteration)
-                for (uint32_t j = 0; j <= r->win_k && r->win_k; j++) {
-                    const uint64_t bound = r->win_row[j];
-                    r->win_cnt_dd[j][sd] = (uint32_t)(std::partition_point(lo, lo + kept, [&](uint32_t row) { return row < bound; }) - lo);
-                }
-            }
-            for (uint32_t j = 0; j <= r->win_k && r->win_k; j++) {
-                const uint64_t bound = r->win_row[j];
-                r->win_alias[j] = (uint64_t)(std::partition_point(alias.begin(), alias.end(), [&](uint64_t e) { return (e & 0xffffffffull) < bound; }) - alias.begin());
-            }
-            for (int k = 0; k < 3; k++) {
-                d.rowlist[k] = r->rowlist[k];
-                if (is_alias[k].empty()) continue;
-                if (hipMalloc((void **)&r->rowlist_dd[k], dd[k].size() * 4 + 4) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
-                if (!dd[k].empty() && hipMemcpy(r->rowlist_dd[k], dd[k].data(), dd[k].size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
-                d.rowlist[k] = r->rowlist_dd[k];
-            }
-            if (hipMalloc((void **)&r->d_alias, alias.size() * 8) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
-            if (hipMemcpy(r->d_alias, alias.data(), alias.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
-            r->n_alias = alias.size();
-        }
-        if (getenv("FK_GATES_TRACE")) fprintf(stderr, "[fk] r1cs load: %.2f s so far, alias plan done (%llu aliases for %llu terms)\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_load0).count(),
-                                              (unsigned long long)r->n_alias, (unsigned long long)r->alias_terms);
-    }
-    if (copies > 1 && wave_copies && copies >= wave_copies && r->bins.mask && cs->num_gates < ((uint64_t)1 << 30)) {
-        std::vector<uint32_t> wl;
-        for (uint64_t g = 0; g < cs->num_gates; g++)
-            for (uint32_t k = 0; k < 3; k++) {
-                const uint64_t l = ptrs[k][g + 1] - ptrs[k][g];
-                if (((r->bins.mask >> k) & 1) && l >= wave_lo && l < wave_hi) wl.push_back(k << 30 | (uint32_t)g);
-            }
-        if (!wl.empty() && (uint64_t)((copies + 63) / 64) * wl.size() < 0xfffffff0ull) {
-            if (hipMalloc((void **)&r->d_wavelist, wl.size() * 4) != hipSuccess) { ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM); }
-            if (hipMemcpy(r->d_wavelist, wl.data(), wl.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
-            r->n_wavelist = (uint32_t)wl.size();
-        }
-    }
-    if (copies > 1) {      // density maps of the whole batch: every copy repeats the instance's pattern, ONE is shared
-        auto rep = [&](std::vector<uint8_t> &f, size_t skip, size_t per) {
-            std::vector<uint8_t> o(skip + per * copies + (skip + per * copies == 0));
-            for (size_t i = 0; i < skip; i++) o[i] = f[i];
-            for (uint32_t j = 0; j < copies; j++) for (size_t i = 0; i < per; i++) o[skip + j * per + i] = f[skip + i];
-            f.swap(o);
-        };
-        rep(a_aux, 0, cs->num_aux); rep(b_aux, 0, cs->num_aux); rep(b_in, 1, cs->num_input - 1);
-    }
-    r->n_table = table.size();
-    if (hipMalloc((void **)&r->table, table.size() * sizeof(Fr)) != hipSuccess || hipMalloc((void **)&r->d_a_aux, a_aux.size()) != hipSuccess ||
-        hipMalloc((void **)&r->d_b_in, b_in.size()) != hipSuccess || hipMalloc((void **)&r->d_b_aux, b_aux.size()) != hipSuccess) {
-        ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM);
-    }
-    if (hipMemcpy(r->table, table.data(), table.size() * sizeof(Fr), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r->d_a_aux, a_aux.data(), a_aux.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r->d_b_in, b_in.data(), b_in.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(r->d_b_aux, b_aux.data(), b_aux.size(), hipMemcpyHostToDevice) != hipSuccess) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
-    for (uint32_t j = 0; j < r->num_aux; j++) { r->n_a_aux += a_aux[j]; r->n_b_aux += b_aux[j]; }
-    for (uint32_t i = 0; i < r->num_input; i++) r->n_b_in += b_in[i];
-    {   // query index lists (bellman's order: inputs first, then the aux variables the density map selects)
-        std::vector<uint32_t> ia, ib;
-        ia.reserve(r->num_input + r->n_a_aux); ib.reserve(r->n_b_in + r->n_b_aux);
-        for (uint32_t i = 0; i < r->num_input; i++) { ia.push_back(i); if (b_in[i]) ib.push_back(i); }
-        for (uint32_t j = 0; j < r->num_aux; j++) { if (a_aux[j]) ia.push_back(r->num_input + j); if (b_aux[j]) ib.push_back(r->num_input + j); }
-        if (hipMalloc((void **)&r->d_idx_a, ia.size() * 4 + 4) != hipSuccess || hipMalloc((void **)&r->d_idx_b, ib.size() * 4 + 4) != hipSuccess) {
-            ctx->err = "r1cs: device allocation failed"; return fail(FK_ERR_OOM);
-        }
-        if ((ia.size() && hipMemcpy(r->d_idx_a, ia.data(), ia.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-            (ib.size() && hipMemcpy(r->d_idx_b, ib.data(), ib.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) { ctx->err = "r1cs: upload failed"; return fail(FK_ERR_HIP); }
-        r->qidx.a = r->d_idx_a; r->qidx.b = r->d_idx_b; r->qidx.n_a = ia.size(); r->qidx.n_b = ib.size();
-        // what a key's padded A array (msm.hip: key_a_pad) is cached under: which aux variables the A query takes
-        const int rcf = query_fingerprint(ctx, r->d_idx_a, ia.size(), &r->qidx.a_fp);
-        if (rcf != FK_OK) return fail(rcf);
-        r->qidx.a_fp_valid = true;
-    }
-    *out = r;
-    return FK_OK;
-}
-
 int fk_r1cs_load(fk_ctx *ctx, const fk_r1cs *cs, fk_r1cs_dev **out) { return fk_guard(ctx, [&]() -> int { return r1cs_load_impl(ctx, cs, 1, out); }); }
-}  // extern "C"
-namespace fk {
-int r1cs_load_coded(fk_ctx *ctx, uint32_t num_input, uint32_t num_aux, uint64_t num_gates, const uint64_t *const ptr[3], const uint32_t *const col[3],
-                    const uint32_t *const cidx[3], const Fr *table, uint64_t n_table, fk_r1cs_dev **out, const uint8_t *const density[3]) {
-    fk_r1cs cs{};
-    cs.num_input = num_input; cs.num_aux = num_aux; cs.num_gates = num_gates;
-    cs.a_ptr = ptr[0]; cs.a_col = col[0]; cs.b_ptr = ptr[1]; cs.b_col = col[1]; cs.c_ptr = ptr[2]; cs.c_col = col[2];
-    return r1cs_load_impl(ctx, &cs, 1, out, cidx, table, n_table, density);
-}
-}  // namespace fk
-extern "C" {
 int fk_r1cs_load_tiled(fk_ctx *ctx, const fk_r1cs *instance, uint32_t copies, fk_r1cs_dev **out) { return fk_guard(ctx, [&]() -> int { return r1cs_load_impl(ctx, instance, copies, out); }); }
 
 // the same system with its coefficients already dictionary-coded by the caller: *_val of `cs` are ignored, cidx[k][i] indexes
@@ -678,8 +330,6 @@ int fk_r1cs_load_coded(fk_ctx *ctx, const fk_r1cs *cs, const uint32_t *a_cidx, c
     if (!ctx) return FK_ERR_BAD_ARG;
     if (!cs || !table || !n_table || !out) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: null argument");
     const uint32_t *cidx[3] = {a_cidx, b_cidx, c_cidx};
-    const uint64_t *ptrs[3] = {cs->a_ptr, cs->b_ptr, cs->c_ptr};
-    for (int k = 0; k < 3; k++) if (ptrs[k] && ptrs[k][cs->num_gates] && !cidx[k]) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: null coefficient index array");
     return r1cs_load_impl(ctx, cs, 1, out, cidx, (const Fr *)table, n_table);
 }); }
 
@@ -704,17 +354,17 @@ int fk_r1cs_alias_info(const fk_r1cs_dev *r, uint64_t out[4]) {
     return FK_OK;
 }
 
+static void alias_unpack(uint64_t e, uint32_t *dst_mtx, uint32_t *dst_row, uint32_t *src_mtx, uint32_t *src_row) {
+    *dst_row = (uint32_t)e; *src_row = (uint32_t)e - ((uint32_t)(e >> 32) & 0xffffu);
+    *dst_mtx = (uint32_t)(e >> 48) & 3u; *src_mtx = (uint32_t)(e >> 50) & 3u;
+}
 int fk_r1cs_aliases(const fk_r1cs_dev *r, uint64_t cap, uint32_t *dst_mtx, uint32_t *dst_row, uint32_t *src_mtx, uint32_t *src_row) {
     if (!r || !dst_mtx || !dst_row || !src_mtx || !src_row || cap < r->n_alias) return FK_ERR_BAD_ARG;
     if (!r->n_alias) return FK_OK;
     try {
         std::vector<uint64_t> h(r->n_alias);
         if (hipMemcpy(h.data(), r->d_alias, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return FK_ERR_HIP;
-        for (uint64_t i = 0; i < h.size(); i++) {
-            const uint64_t e = h[i];
-            dst_row[i] = (uint32_t)e; src_row[i] = (uint32_t)e - ((uint32_t)(e >> 32) & 0xffffu);
-            dst_mtx[i] = (uint32_t)(e >> 48) & 3u; src_mtx[i] = (uint32_t)(e >> 50) & 3u;
-        }
+        for (uint64_t i = 0; i < h.size(); i++) alias_unpack(h[i], &dst_mtx[i], &dst_row[i], &src_mtx[i], &src_row[i]);
     } catch (...) { return FK_ERR_OOM; }
     return FK_OK;
 }
@@ -726,6 +376,46 @@ int fk_r1cs_windows(const fk_r1cs_dev *r, uint32_t *n_windows, uint64_t rows[17]
     for (uint32_t j = 0; j < r->win_k && need; j++) need[j] = r->win_need[j];
     return FK_OK;
 }
+
+// inspection for the tests: the loader's stages (spmv_plan.hpp) in the loader's order, without its uploads; host only
+static void plan_segs_out(const BinArgs &b, fk_r1cs_plan_segs *o) {
+    static_assert(FK_PLAN_SEGS == SPMV_SEGS && FK_PLAN_WIN_MAX == fk_r1cs_dev::WIN_MAX, "fawkes_hip_inspect.h mirrors r1cs.hpp");
+    o->nseg = b.nseg; o->mask = b.mask;
+    memcpy(o->mtx, b.mtx, sizeof b.mtx); memcpy(o->lg, b.lg, sizeof b.lg); memcpy(o->rows, b.n_rows, sizeof b.n_rows);
+    memcpy(o->list_off, b.list_off, sizeof b.list_off); memcpy(o->first_block, b.first_block, sizeof b.first_block);
+}
+int fk_r1cs_plan_host(const fk_r1cs *cs, uint32_t copies, const uint32_t *a_cidx, const uint32_t *b_cidx, const uint32_t *c_cidx, const uint64_t *table,
+                      uint64_t n_table, fk_r1cs_plan_info *out) { return fk_guard((fk_ctx *)nullptr, [&]() -> int {
+    if (!cs || !out) return FK_ERR_BAD_ARG;
+    const uint32_t *cidx[3] = {a_cidx, b_cidx, c_cidx};
+    const bool coded = a_cidx || b_cidx || c_cidx || table;
+    SpmvPlan p(cs, copies, coded ? cidx : nullptr, (const Fr *)table, n_table, nullptr, tls_error());
+    fk_r1cs_dev r;           // its plain fields and h_rowlist; no device array is ever allocated
+    FK_TRY(plan_validate(p, r));
+    FK_TRY(plan_class_lists(p, r));
+    for (int k = 0; k < 3; k++) FK_TRY(plan_coefficients(p, r, k));
+    plan_windows(p, r);
+    FK_TRY(plan_aliases(p, r));
+    FK_TRY(plan_dedup(p, r));
+    plan_wavelist(p, r);
+    plan_queries(p, r);
+    auto put = [](uint32_t *dst, const std::vector<uint32_t> &v) { if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * 4); };
+    plan_segs_out(r.bins, &out->segs); plan_segs_out(r.bins_dd, &out->segs_dd);
+    for (int k = 0; k < 3; k++) {
+        put(out->list[k], r.h_rowlist[k]); put(out->list_dd[k], p.dd[k]);
+        out->own_dd[k] = !p.is_alias[k].empty(); out->n_dd[k] = (uint32_t)p.dd[k].size();
+        out->wave_from[k] = r.wave_from[k]; out->wave_to[k] = r.wave_to[k];
+    }
+    for (uint64_t i = 0; i < p.alias.size() && out->alias_dst_mtx && out->alias_dst_row && out->alias_src_mtx && out->alias_src_row; i++)
+        alias_unpack(p.alias[i], &out->alias_dst_mtx[i], &out->alias_dst_row[i], &out->alias_src_mtx[i], &out->alias_src_row[i]);
+    put(out->idx_a, p.idx_a); put(out->idx_b, p.idx_b);
+    out->win_k = r.win_k;
+    memcpy(out->win_row, r.win_row, sizeof r.win_row); memcpy(out->win_alias, r.win_alias, sizeof r.win_alias);
+    memcpy(out->win_cnt, r.win_cnt, sizeof r.win_cnt); memcpy(out->win_cnt_dd, r.win_cnt_dd, sizeof r.win_cnt_dd);
+    out->n_alias = r.n_alias; out->alias_terms = r.n_alias ? r.alias_terms : 0; out->alias_min = r.alias_min; out->alias_lookback = r.alias_lookback;
+    out->n_idx_a = p.idx_a.size(); out->n_idx_b = p.idx_b.size();
+    return FK_OK;
+}); }
 
 }  // extern "C"
 namespace fk {
@@ -748,8 +438,7 @@ static int slice_lists(fk_ctx *ctx, const fk_r1cs_dev *r, uint32_t log_w, const 
                 for (uint32_t q = 0; q < W; q++) { sl.cnt[s][q] = c[q]; sl.offs[s][q] = acc; pos[q] = acc; acc += c[q]; }
                 for (uint32_t i = 0; i < nr; i++) { const uint32_t row = src[off + i]; dst[off + pos[row & (W - 1)]++] = row; }   // stable: longest first inside a group
             }
-            FK_HIP(ctx, hipMalloc((void **)&sl.d_list[k], dst.size() * 4 + 4));
-            if (!dst.empty()) FK_HIP(ctx, hipMemcpy(sl.d_list[k], dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
+            FK_TRY(dev_upload(ctx, sl.d_list[k], dst.data(), dst.size(), 1));        // (a call that fails here leaves built false: the next one allocates afresh)
         }
         sl.built = true;
     }
@@ -809,16 +498,13 @@ int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a
             while ((uint32_t)((uint64_t)P * g) & (W - 1)) P++;
             sa.P = P;
             for (uint32_t p_ = 0; p_ < P; p_++) sa.rho[p_] = (uint32_t)((rank + W * P - ((uint64_t)p_ * g & (W - 1))) & (W - 1));
-            b.first_block[0] = 0;
             for (uint32_t s = 0; s < b.nseg; s++) {
                 memcpy(sa.cnt[s], sl->cnt[s], sizeof sa.cnt[s]); memcpy(sa.offs[s], sl->offs[s], sizeof sa.offs[s]);
                 uint64_t T = 0, part = 0;
                 const uint32_t tail = r->copies % P;
                 for (uint32_t p_ = 0; p_ < P; p_++) { T += sa.cnt[s][sa.rho[p_]]; if (p_ < tail) part += sa.cnt[s][sa.rho[p_]]; }
                 sa.T[s] = (uint32_t)T;
-                const uint64_t groups = (uint64_t)(r->copies / P) * T + part, per = 256u >> b.lg[s], blocks = (groups + per - 1) / per;
-                if (b.first_block[s] + blocks > 0x7fffffffull) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "r1cs: system too large for the binned product");
-                b.first_block[s + 1] = b.first_block[s] + (uint32_t)blocks;
+                FK_TRY(bin_segment(ctx->err, b, s, b.mtx[s], b.lg[s], b.list_off[s], b.n_rows[s], (uint64_t)(r->copies / P) * T + part));
             }
             for (int k = 0; k < 3; k++) b.rowlist[k] = sl->d_list[k];
         }
@@ -826,26 +512,20 @@ int r1cs_eval_impl(fk_ctx *ctx, const fk_r1cs_dev *r, const void *d_z, void *d_a
             // rows of wave_lo .. wave_hi - 1 terms go to spmv_tiled_wave_kernel: they are rowlist[wave_from, wave_to) of their matrix
             // (the lists are sorted by length, longest first), i.e. with the default [4, 64): the whole 8-, 4- and 2-lane classes and the
             // 4 .. 7-term head of the one-lane class; with wave_hi > 64 also the tail of the 16-lane class
-            b.first_block[0] = 0;
             for (uint32_t s = 0; s < b.nseg; s++) {
                 const uint32_t k = b.mtx[s], s0 = b.list_off[s], s1 = s0 + b.n_rows[s], w0 = r->wave_from[k], w1 = r->wave_to[k];
                 uint32_t lo = s0, hi = s1;
                 if (w0 <= s0) lo = std::min(std::max(s0, w1), s1); else hi = std::min(s1, w0);      // (load keeps the wave range from lying strictly inside a class)
-                b.list_off[s] = lo; b.n_rows[s] = hi - lo;
-                const uint64_t groups = (uint64_t)b.n_rows[s] * r->copies, per = 256u >> b.lg[s];
-                b.first_block[s + 1] = b.first_block[s] + (uint32_t)((groups + per - 1) / per);
+                FK_TRY(bin_segment(ctx->err, b, s, k, b.lg[s], lo, hi - lo, (uint64_t)(hi - lo) * r->copies));
             }
             const uint64_t n_waves = (uint64_t)((r->copies + 63) / 64) * r->n_wavelist;
             hipLaunchKernelGGL(spmv_tiled_wave_kernel, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, ctx->stream, a, r->table, (const Fr *)d_z, r->num_input, td,
                                r->copies, r->d_wavelist, r->n_wavelist, (uint32_t)n_waves);
         }
         if (window >= 0) {
-            b.first_block[0] = 0;
             for (uint32_t s = 0; s < b.nseg; s++) {
                 const uint32_t c0 = (dedup ? r->win_cnt_dd : r->win_cnt)[window][s], c1 = (dedup ? r->win_cnt_dd : r->win_cnt)[window + 1][s];
-                b.list_off[s] += c0; b.n_rows[s] = c1 - c0;
-                const uint64_t per = 256u >> b.lg[s];
-                b.first_block[s + 1] = b.first_block[s] + (uint32_t)((b.n_rows[s] + per - 1) / per);
+                FK_TRY(bin_segment(ctx->err, b, s, b.mtx[s], b.lg[s], b.list_off[s] + c0, c1 - c0, c1 - c0));
             }
         }
         const unsigned blocks = b.first_block[b.nseg];

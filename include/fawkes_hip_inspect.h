@@ -15,6 +15,35 @@ int fk_r1cs_alias_info(const fk_r1cs_dev *r1cs, uint64_t out[4]);
 /* the table, sorted by (dst row, dst matrix); matrices 0 = A, 1 = B, 2 = C; cap: elements each array holds (>= out[0] above) */
 int fk_r1cs_aliases(const fk_r1cs_dev *r1cs, uint64_t cap, uint32_t *dst_mtx, uint32_t *dst_row, uint32_t *src_mtx, uint32_t *src_row);
 
+/* The plan the loader of a resident constraint system makes, on the host alone: no context, no GPU.  It runs the loader's own stages
+ * (csrc/spmv_plan.hpp) over `cs` standing for `copies` of itself and reports what they decide.  a_cidx / b_cidx / c_cidx, table, n_table: as
+ * fk_r1cs_load_coded takes them, or all NULL / 0 for the coefficients of `cs` (its *_val; NULL there: every coefficient ONE).
+ * The caller allocates the arrays of `out` (any may be NULL: not wanted): list / list_dd num_gates elements each, the four alias arrays
+ * 3 * num_gates, idx_a / idx_b as many as the `copies` systems have variables.  A refusal returns the loader's code; fk_last_error(NULL)
+ * has its text.  Row windows: win_need is not reported, it is read off the columns on the device. */
+#define FK_PLAN_SEGS 15
+#define FK_PLAN_WIN_MAX 16
+typedef struct {
+    uint32_t nseg, mask;                          /* mask: bit k = matrix k has class lists */
+    uint32_t mtx[FK_PLAN_SEGS], lg[FK_PLAN_SEGS], rows[FK_PLAN_SEGS], list_off[FK_PLAN_SEGS], first_block[FK_PLAN_SEGS + 1];
+} fk_r1cs_plan_segs;
+typedef struct {
+    uint32_t *list[3];                            /* in: the class lists, per matrix (written where the matrix is binned) */
+    uint32_t *list_dd[3];                         /* in: the dedup lists (written where own_dd[k]; n_dd[k] entries) */
+    uint32_t *alias_dst_mtx, *alias_dst_row, *alias_src_mtx, *alias_src_row;     /* in: the alias table as fk_r1cs_aliases gives it */
+    uint32_t *idx_a, *idx_b;                      /* in: the A / B query index lists */
+    fk_r1cs_plan_segs segs, segs_dd;              /* the launch segments of the full lists and of the dedup lists (n_alias > 0) */
+    uint32_t own_dd[3], n_dd[3];                  /* matrix k has a dedup list of its own (else its segments of segs_dd point into list[k]) */
+    uint32_t wave_from[3], wave_to[3];            /* list[k][wave_from .. wave_to): the rows the tiled wave kernel takes */
+    uint32_t win_k;                               /* row windows (0: none) */
+    uint64_t win_row[FK_PLAN_WIN_MAX + 1], win_alias[FK_PLAN_WIN_MAX + 1];
+    uint32_t win_cnt[FK_PLAN_WIN_MAX + 1][FK_PLAN_SEGS], win_cnt_dd[FK_PLAN_WIN_MAX + 1][FK_PLAN_SEGS];
+    uint64_t n_alias, alias_terms, alias_min, alias_lookback;
+    uint64_t n_idx_a, n_idx_b;
+} fk_r1cs_plan_info;
+int fk_r1cs_plan_host(const fk_r1cs *cs, uint32_t copies, const uint32_t *a_cidx, const uint32_t *b_cidx, const uint32_t *c_cidx, const uint64_t *table,
+                      uint64_t n_table, fk_r1cs_plan_info *out);
+
 /* A adopts L's bucket sort (csrc/msm.hip: key_a_pad) where both slices of the key are whole, the domain is at most 2^25 and a resident
  * constraint system gives the A query: the key then keeps A's aux bases a second time, laid out in L's index space (infinity where a variable
  * takes no part in A) with levels of their own, beside a's array and levels, which stay as they are.  One such array per A query, at most

@@ -74,6 +74,9 @@ def test_r1cs_load_rejects_bad_input(ctx):
     bad = (ptr, np.array([9], np.uint32), one.reshape(1, 4))
     with pytest.raises(fk.FkError):
         ctx.load_r1cs(fk.R1cs(1, 1, bad, good, good))
+    coded = (ptr, np.array([1], np.uint32), np.array([0], np.uint32))
+    with pytest.raises(fk.FkError, match='coefficient table must start with ONE'):
+        ctx.load_r1cs_coded(1, 1, [coded] * 3, fx.mont_fr(2).reshape(1, 4))
 
 
 def _ragged_system(seed, lens_choices, gates, nin, naux):

@@ -14,10 +14,10 @@ import pytest
 import bn254_ref as ref
 import fixtures as fx
 from helpers import r1cs_product, TOXIC
+from spmv_plan_cases import BIN_MIN, crafted_system, reference_aliases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN_MIN = 8          # a matrix with a row this long has the length-class lists (spmv.hip: bin_min)
 
 
 def alias_info(dr):
@@ -35,35 +35,6 @@ def alias_table(dr):
     fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
     assert fn(dr.handle, n, *[a.ctypes.data for a in arr]) == 0
     return [tuple(int(a[i]) for a in arr) for i in range(n)]          # (dst matrix, dst row, src matrix, src row)
-
-
-def reference_aliases(mats, min_len, lookback, bin_min=BIN_MIN):
-    """The rule, restated: gates in row order, matrices A, B, C inside a gate.  A row of >= min_len terms of a binned matrix is an alias of
-    the EARLIEST row, of any matrix, at most `lookback` gates back (its own gate included, matrices before it) whose column sequence and
-    coefficient-index sequence are identical and which is not an alias itself.  mats: three (ptr, col, cidx).  Returns
-    ([(dst matrix, dst row, src matrix, src row)] in (dst row, dst matrix) order, terms the aliases stand for)."""
-    gates = len(mats[0][0]) - 1
-    ptrs = [np.asarray(m[0]).astype(np.int64) for m in mats]
-    binned = [gates > 0 and int(np.diff(p).max(initial=0)) >= bin_min for p in ptrs]
-    window, out, terms = [], [], 0            # window: per gate, [(matrix, content, is alias)]
-    for g in range(gates):
-        cur = []
-        window.append((g, cur))
-        if len(window) > lookback + 1:
-            window.pop(0)
-        for k in range(3):
-            lo, hi = int(ptrs[k][g]), int(ptrs[k][g + 1])
-            if hi - lo < min_len:
-                continue
-            content = (mats[k][1][lo:hi].tobytes(), mats[k][2][lo:hi].tobytes())
-            src = None
-            if binned[k]:
-                src = next(((k2, g2) for g2, rows in window for k2, c2, al2 in rows if not al2 and c2 == content), None)
-            if src is not None:
-                out.append((k, g, src[0], src[1]))
-                terms += hi - lo
-            cur.append((k, content, src is not None))
-    return out, terms
 
 
 def random_z(nv, seed):
@@ -105,62 +76,6 @@ def knobs(ctx):
 
 
 # ---------------------------------------------------------------- 1. crafted system
-def crafted_system(min_len, back, c_short, seed=7):
-    """~3000 gates of random short and middling rows with every case planted 40 gates apart.  c_short: C's rows stay below BIN_MIN terms,
-    so C has no class lists -- its rows can be sources and never destinations.  Returns (R1csC, [(ptr, col, cidx)] * 3, expected aliases,
-    rows that must not be aliases)."""
-    rng = np.random.default_rng(seed)
-    gates, nin, naux = 3000, 3, 3100
-    nv = nin + naux
-    coeffs = fx.co.limbs_arr([1, ref.R - 1, 2] + [int(x) for x in rng.integers(3, 2**62, 40)])
-    coeffs = np.stack([fx.mont_fr(int.from_bytes(c.tobytes(), 'little')) for c in coeffs])
-
-    def row(n):
-        return rng.integers(0, nv, n).astype(np.uint32), rng.integers(0, len(coeffs), n).astype(np.uint32)
-
-    fill = [[0, 1, 1, 2, 3, 5, 9, 20], [0, 1, 1, 2, 3, 4, 8, 33], [0, 1, 2, 3] if c_short else [0, 1, 2, 3, 5, 12, 40]]
-    rows = [[row(int(n)) for n in rng.choice(fill[k], size=gates)] for k in range(3)]
-    A, B, Cm = 0, 1, 2
-    want, never = [], []
-    p = [20]
-
-    def site():
-        p[0] += 40
-        assert back < 18 and p[0] + 2 * back + 2 < gates
-        return p[0] - 40
-
-    for n in (3, 4, 7, 8, 15, 16, 31, 32, 63, 64, 65, 512):          # every class boundary; A row g = B row g
-        g = site()
-        rows[A][g] = rows[B][g] = row(n)
-        (want if n >= min_len else never).append((B, g, A, g))
-    g = site(); rows[A][g] = rows[B][g + 2] = row(20); want.append((B, g + 2, A, g))                      # A row g = B row g + 2
-    g = site(); rows[A][g] = rows[B][g + 1] = rows[A][g + 2] = row(17)                                      # three times
-    want += [(B, g + 1, A, g), (A, g + 2, A, g)]
-    g = site(); rows[A][g] = rows[B][g] = rows[A][g + back // 2] = rows[B][g + back] = row(33)              # four times: all point at the first
-    want += [(B, g, A, g), (A, g + back // 2, A, g), (B, g + back, A, g)]
-    g = site(); rows[Cm][g] = rows[A][g + 1] = row(5 if c_short else 16); want.append((A, g + 1, Cm, g))   # source in C, destination in A
-    g = site(); c, i = row(24); i2 = i.copy(); i2[11] = (i2[11] + 1) % len(coeffs)                         # one coefficient index differs
-    rows[A][g], rows[B][g] = (c, i), (c, i2); never.append((B, g, A, g))
-    g = site(); c, i = row(24); perm = np.roll(np.arange(24), 1)                                            # same terms, another order
-    rows[A][g], rows[B][g] = (c, i), (c[perm], i[perm]); never.append((B, g, A, g))
-    g = site(); rows[A][g] = rows[A][g + back] = row(12); want.append((A, g + back, A, g))                  # exactly `back` gates apart
-    g = site(); rows[A][g] = rows[A][g + back + 1] = row(12); never.append((A, g + back + 1, A, g))        # one gate further
-    g = site(); rows[B][g] = rows[B][g + back] = rows[B][g + 2 * back] = row(9)                             # the middle one is an alias: no source for the third
-    want.append((B, g + back, B, g)); never.append((B, g + 2 * back, B, g + back)); never.append((B, g + 2 * back, B, g))
-    if c_short:                                                                                             # an unbinned matrix's repeat is never a destination
-        g = site(); rows[A][g] = rows[Cm][g] = row(6); never.append((Cm, g, A, g))
-
-    mats, csrs = [], []
-    for k in range(3):
-        ptr = np.zeros(gates + 1, np.uint64)
-        ptr[1:] = np.cumsum([len(r[0]) for r in rows[k]])
-        col = np.concatenate([r[0] for r in rows[k]]).astype(np.uint32)
-        cidx = np.concatenate([r[1] for r in rows[k]]).astype(np.uint32)
-        mats.append((ptr, col, cidx))
-        csrs.append(fx.co.Csr(ptr, col, np.ascontiguousarray(coeffs[cidx])))
-    return fx.co.R1csC(nin, naux, *csrs), mats, want, never
-
-
 @pytest.mark.parametrize('c_short', [False, True])
 def test_crafted_repeats(ctx, oracle, knobs, c_short):
     min_len, back = knobs
