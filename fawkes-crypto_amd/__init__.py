@@ -27,3 +27,4 @@ from .sparse_merkle import SparseMerkleTree  # noqa: F401
 from . import merkle_set  # noqa: F401
 from . import batch  # noqa: F401
 from .batch import prove_batch, prove_batch_dev, prove_given_batch  # noqa: F401
+from . import ceremony  # noqa: F401

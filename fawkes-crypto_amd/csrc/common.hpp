@@ -69,6 +69,7 @@ struct CtxScratch {
     // bt_z: the witnesses of fk_prove_batch (host rows); bt_sort: histogram, bucket and segment offsets; bt_io: r, s, the five sums per proof, the proofs
     DevBuf bt_vec, bt_z, bt_sort, bt_entries, bt_partial, bt_wsum, bt_io, bt_scan;
     DevBuf bt_check;  // batch_check.hip: one record (fk_check_report) per proof of a group
+    DevBuf ceremony;  // ceremony.hip: the weights of a contribution check, max(n_h, n_l) Montgomery Fr
     DevBuf *begin() { return &misc; }
     DevBuf *end() { return begin() + sizeof(CtxScratch) / sizeof(DevBuf); }
     void release_scratch() { for (DevBuf *b = begin(); b != end(); ++b) b->release(); }

@@ -159,6 +159,14 @@ using G2Affine = Affine<Fq2>;
 using G1Xyzz = Xyzz<Fq>;
 using G2Xyzz = Xyzz<Fq2>;
 
+// k * p on the host for a Montgomery k, affine in and out: the vk points of a setup, the deltas of a ceremony contribution, and the
+// reference the scale kernel of ceremony.hip is compared with
+template <class F>
+static inline Affine<F> host_mul(const Affine<F> &p, const Fr &k_mont) {
+    const Fr k = Fr::from_mont(k_mont);
+    return Xyzz<F>::mul_scalar(Xyzz<F>::from_affine(p), k.v).to_affine();
+}
+
 // The key's five points that enter every proof.
 struct AssembleKey { G1Affine alpha_g1, beta_g1, delta_g1; G2Affine beta_g2, delta_g2; };
 

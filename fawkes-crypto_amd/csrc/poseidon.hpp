@@ -133,10 +133,10 @@ static void keccak256(const uint8_t *data, size_t len, uint8_t out[32]) {
     for (int i = 0; i < 4; i++) for (int b = 0; b < 8; b++) out[8 * i + b] = (uint8_t)(a[i] >> (8 * b));
 }
 
-static inline uint32_t rol32(uint32_t v, unsigned n) { return (v << n) | (v >> (32 - n)); }
+static FK_HD uint32_t rol32(uint32_t v, unsigned n) { return (v << n) | (v >> (32 - n)); }
 
-// one ChaCha20 block: constants | 256-bit key | 64-bit block counter | 64-bit stream id
-static void chacha20_block(const uint32_t key[8], uint64_t counter, uint64_t stream, uint32_t out[16]) {
+// one ChaCha20 block: constants | 256-bit key | 64-bit block counter | 64-bit stream id (host and device: ceremony.hip draws weights on both)
+static FK_HD void chacha20_block(const uint32_t key[8], uint64_t counter, uint64_t stream, uint32_t out[16]) {
     uint32_t s[16] = {0x61707865, 0x3320646e, 0x79622d32, 0x6b206574};
     for (int i = 0; i < 8; i++) s[4 + i] = key[i];
     s[12] = (uint32_t)counter; s[13] = (uint32_t)(counter >> 32); s[14] = (uint32_t)stream; s[15] = (uint32_t)(stream >> 32);

@@ -225,12 +225,6 @@ static std::vector<Affine<F>> host_fb_table(const Affine<F> &g) {
     return out;
 }
 
-template <class F>
-static Affine<F> host_mul(const Affine<F> &p, const Fr &k_mont) {
-    const Fr k = Fr::from_mont(k_mont);
-    return Xyzz<F>::mul_scalar(Xyzz<F>::from_affine(p), k.v).to_affine();
-}
-
 static Fr fr_load(const uint64_t *p) { Fr r; memcpy(&r, p, 32); return r; }
 
 }  // namespace fk
