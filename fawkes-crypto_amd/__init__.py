@@ -28,3 +28,7 @@ from . import merkle_set  # noqa: F401
 from . import batch  # noqa: F401
 from .batch import prove_batch, prove_batch_dev, prove_given_batch  # noqa: F401
 from . import ceremony  # noqa: F401
+from . import ceremony_init  # noqa: F401
+from .ceremony_init import (  # noqa: F401
+    PowersOfTau, PowersReport, g1_ntt, g2_ntt, initial_key, initial_key_host, initial_image, check_powers, check_powers_host,
+)

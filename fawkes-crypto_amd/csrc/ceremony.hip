@@ -4,11 +4,9 @@
 // the host; a, b_g1, b_g2 copied device to device.  Check: four multi-scalar multiplications with 128-bit weights from a ChaCha20 stream
 // (weights_kernel; the existing MSM over the keys' own arrays), a word compare of the fixed arrays (words_differ_kernel), six Miller
 // loops and three final exponentiations on the host (pairing.hpp).  The host entries are the plain references the device is compared with.
-#include "pairing.hpp"
+#include "ceremony_shared.hpp"   // generators, pairing_eq, lanes_claim, draw_seed, host_entry
 #include "poseidon.hpp"          // chacha20_block, Seedbox::fr_below_modulus, fr_from_limbs
 #include "../../include/fawkes_hip_ceremony.h"
-#include <sys/random.h>
-#include <errno.h>
 #include <memory>
 
 namespace fk {
@@ -150,21 +148,6 @@ __global__ __launch_bounds__(256) void words_differ_kernel(const uint64_t *__res
     if (acc) atomicOr(flag, (unsigned long long)acc);
 }
 
-static G1Affine g1_gen() { return G1Affine{Fq::one(), Fq::dbl(Fq::one())}; }
-static G2Affine g2_gen() {
-    const uint32_t x0[8] = FK_G2_GEN_X0, x1[8] = FK_G2_GEN_X1, y0[8] = FK_G2_GEN_Y0, y1[8] = FK_G2_GEN_Y1;
-    G2Affine g;
-    for (int i = 0; i < 8; i++) { g.x.c0.v[i] = x0[i]; g.x.c1.v[i] = x1[i]; g.y.c0.v[i] = y0[i]; g.y.c1.v[i] = y1[i]; }
-    return g;
-}
-
-// e(p1, q1) == e(p2, q2); a pairing with the point at infinity on either side is one
-static bool pairing_eq(const G1Affine &p1, const G2Affine &q1, const G1Affine &p2, const G2Affine &q2) {
-    using F12 = Fq12T<Fq>;
-    const F12 m = F12::mul(miller_loop_proj<Fq>(p1, q1), miller_loop_proj<Fq>(affine_neg_if(p2, true), q2));
-    return final_exponentiation<Fq>(m).is_one();
-}
-
 // what a check reads of one key besides its arrays
 struct KeyHead {
     uint64_t m, num_input, num_aux, n_h, n_l, n_a, n_b;
@@ -219,23 +202,6 @@ static int key_ok(fk_ctx *ctx, const fk_key *k, const char *who) {
     return FK_OK;
 }
 
-// the device entries run on the lanes of the multi-scalar multiplication (check) or size fixed-base levels against free memory
-// (contribute): not beside a proof that holds lanes or staging between two calls
-static int lanes_claim(fk_ctx *ctx, const char *who) {
-    if (proof_holds_lanes(ctx)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "%s: a proof holds this context's lanes or staging buffers (collect it first: fk_prove_msms_finish_dev / fk_prove_r1cs_wait)", who);
-    return scratch_claim(ctx, who);
-}
-
-static int draw_seed(fk_ctx *ctx, uint8_t seed[32]) {
-    size_t got = 0;
-    while (got < 32) {
-        const ssize_t r = getrandom(seed + got, 32 - got, 0);
-        if (r < 0) { if (errno == EINTR) continue; FK_SET_ERR(ctx, FK_ERR_UNSUPPORTED, "contribution check: getrandom failed (errno %d): no weights can be drawn", errno); }
-        got += (size_t)r;
-    }
-    return FK_OK;
-}
-
 static int check_host(fk_ctx *ctx, const fk_key_desc *before, const fk_key_desc *after, const uint8_t *seed, fk_contribution_report *report) {
     if (!seed || !report) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "contribution check: null argument");
     FK_TRY(desc_ok(ctx, before, "contribution check (before)"));
@@ -270,7 +236,7 @@ static int check_dev(fk_ctx *ctx, const fk_key *before, const fk_key *after, con
     FK_TRY(key_ok(ctx, before, "contribution check (before)"));
     FK_TRY(key_ok(ctx, after, "contribution check (after)"));
     uint8_t seed[32];
-    if (seed_in) memcpy(seed, seed_in, 32); else FK_TRY(draw_seed(ctx, seed));
+    if (seed_in) memcpy(seed, seed_in, 32); else FK_TRY(draw_seed(ctx, seed, "contribution check"));
     const KeyHead hb = head_of(before), ha = head_of(after);
     const bool shape = same_shape(hb, ha);
     bool arrays = false;
@@ -365,15 +331,6 @@ static int contribute_dev(fk_ctx *ctx, const fk_key *key, const uint64_t x_[4], 
     if (!(flags & FK_KEY_NO_LEVELS)) FK_TRY(key_precompute(ctx, k.get()));
     *out_key = k.release();
     return FK_OK;
-}
-
-// a host-only routine without a context leaves its message in fk_last_error(NULL)
-template <class F>
-static int host_entry(F &&body) {
-    fk_ctx local;
-    const int rc = fk_guard(&local, [&]() -> int { return body(&local); });
-    try { tls_error() = local.err; } catch (...) {}
-    return rc;
 }
 
 }  // namespace fk

@@ -70,6 +70,7 @@ struct CtxScratch {
     DevBuf bt_vec, bt_z, bt_sort, bt_entries, bt_partial, bt_wsum, bt_io, bt_scan;
     DevBuf bt_check;  // batch_check.hip: one record (fk_check_report) per proof of a group
     DevBuf ceremony;  // ceremony.hip: the weights of a contribution check, max(n_h, n_l) Montgomery Fr
+    DevBuf ceremony_init;  // ceremony_init.hip: the Xyzz work array of a transform over points (128 B per G1 point, 256 B per G2 point)
     DevBuf *begin() { return &misc; }
     DevBuf *end() { return begin() + sizeof(CtxScratch) / sizeof(DevBuf); }
     void release_scratch() { for (DevBuf *b = begin(); b != end(); ++b) b->release(); }
