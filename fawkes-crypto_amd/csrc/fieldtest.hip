@@ -1,5 +1,6 @@
-// libfawkes_fieldtest.so: a TEST-ONLY device library (tests/test_gpu_field_ops.py, tests/test_gpu_point_ops.py).  Not part of the
-// product: it is not linked into libfawkes_hip.so and none of its symbols is part of the ABI (include/fawkes_hip.h).
+// libfawkes_fieldtest.so: a TEST-ONLY device library (tests/test_gpu_field_ops.py, tests/test_gpu_point_ops.py; its second source,
+// fieldtest_tower.hip, serves tests/test_tower_host.py and tests/test_gpu_tower_ops.py).  Not part of the product: it is not linked
+// into libfawkes_hip.so and none of its symbols is part of the ABI (include/fawkes_hip.h).
 //
 // Every kernel is a thin wrapper: one thread loads the operands of one case, calls ONE method of field.hpp / curve.hpp exactly as
 // the product spells it, and stores the result.  The methods under test are the device pass of the generated arithmetic
@@ -7,6 +8,9 @@
 //
 // A case is `operands` elements in, `results` elements out, an element being one value of the type under test (8 x u32, or 16 for
 // an Fq2 type: c0 || c1).  Point operations take their coordinates as consecutive elements (Xyzz: x y zz zzz; Affine: x y).
+// Three kinds of operand are raw words in the first 8 words of an element, not field elements and not range-limited: the exponent of
+// pow (8 words), the 64-bit argument of pow_u64 / from_u64 (words 0 and 1), and the scalar of a point multiplication (p_mul_scalar: 8
+// words; p_mul_affine_bits: lo in words 0-1, hi in words 2-3, nbits in word 4, taken as at most 128).
 //
 // Modes -- the ways a wave-level carry chain can go wrong that operand values alone do not show:
 //   straight : the operation, unconditionally (the caller picks n not a multiple of 64: a partial last wave)
@@ -14,10 +18,12 @@
 //              (alt_of) on the same operands: the SGPR-pair carries of both live under a partial EXEC mask
 //   aliased  : the outputs overwrite the inputs in the same call, as curve.hpp does (F::mul2(zz, pp, zzz, ppp, zz, zzz))
 #include "curve.hpp"
+#include "fieldtest.hpp"
 #include <stdio.h>
 #include <type_traits>
 
 using namespace fk;
+using namespace ft;
 
 namespace {
 
@@ -25,16 +31,20 @@ enum { T_FQ, T_FQL, T_FQC, T_FR, T_FRL, T_FQ2, T_FQ2L, T_FQ2C, T_COUNT };
 enum {
     OP_ADD, OP_SUB, OP_DBL, OP_NEG, OP_ADD2, OP_SUB2, OP_ADDSUB2, OP_MUL, OP_SQR, OP_MUL2, OP_SQR2, OP_MULSUB, OP_DOT4,
     OP_IS_ZERO, OP_EQ, OP_CANON, OP_FROM_MONT, OP_TO_MONT,
-    OP_P_ADD_MIXED, OP_P_ADD_MIXED_NZ, OP_P_ADD, OP_P_DBL, OP_P_DBL_AFFINE, OP_P_NEG_IF, OP_P_TO_AFFINE, OP_COUNT
+    OP_P_ADD_MIXED, OP_P_ADD_MIXED_NZ, OP_P_ADD, OP_P_DBL, OP_P_DBL_AFFINE, OP_P_NEG_IF, OP_P_TO_AFFINE,
+    // an id, once given, stays: new operations go to the end, so an older test file still names the kernels it means
+    OP_INV, OP_POW, OP_POW_U64, OP_FROM_U64, OP_P_MUL_SCALAR, OP_P_MUL_AFFINE_BITS,
+    OP_COUNT
 };
 enum { M_STRAIGHT, M_DIVERGENT, M_ALIASED, M_COUNT };
-enum { FT_OK = 0, FT_BAD_ARGUMENT = 1, FT_HIP_ERROR = 2, FT_AFTER_ERROR = 3 };
 
 constexpr int nin_of(int op) {
     switch (op) {
-    case OP_DBL: case OP_NEG: case OP_SQR: case OP_IS_ZERO: case OP_CANON: case OP_FROM_MONT: case OP_TO_MONT: return 1;
-    case OP_ADD: case OP_SUB: case OP_MUL: case OP_SQR2: case OP_EQ: case OP_P_DBL_AFFINE: return 2;
+    case OP_DBL: case OP_NEG: case OP_SQR: case OP_IS_ZERO: case OP_CANON: case OP_FROM_MONT: case OP_TO_MONT: case OP_INV: case OP_FROM_U64: return 1;
+    case OP_ADD: case OP_SUB: case OP_MUL: case OP_SQR2: case OP_EQ: case OP_P_DBL_AFFINE: case OP_POW: case OP_POW_U64: return 2;
     case OP_P_NEG_IF: return 3;                                   // x, y, and an element whose limb 0 bit 0 is the flag
+    case OP_P_MUL_AFFINE_BITS: return 3;                          // x, y, and an element holding lo, hi, nbits
+    case OP_P_MUL_SCALAR: return 5;                               // Xyzz, and an element holding the scalar
     case OP_ADD2: case OP_SUB2: case OP_ADDSUB2: case OP_MUL2: case OP_MULSUB: case OP_P_DBL: case OP_P_TO_AFFINE: return 4;
     case OP_P_ADD_MIXED: case OP_P_ADD_MIXED_NZ: return 6;        // Xyzz accumulator, Affine addend
     case OP_DOT4: case OP_P_ADD: return 8;
@@ -44,7 +54,8 @@ constexpr int nin_of(int op) {
 constexpr int nout_of(int op) {
     switch (op) {
     case OP_ADD2: case OP_SUB2: case OP_ADDSUB2: case OP_MUL2: case OP_SQR2: case OP_P_NEG_IF: case OP_P_TO_AFFINE: return 2;
-    case OP_P_ADD_MIXED: case OP_P_ADD_MIXED_NZ: case OP_P_ADD: case OP_P_DBL: case OP_P_DBL_AFFINE: return 4;
+    case OP_P_ADD_MIXED: case OP_P_ADD_MIXED_NZ: case OP_P_ADD: case OP_P_DBL: case OP_P_DBL_AFFINE:
+    case OP_P_MUL_SCALAR: case OP_P_MUL_AFFINE_BITS: return 4;
     }
     return 1;
 }
@@ -66,6 +77,8 @@ constexpr int alt_of(int op) {
     case OP_DOT4: return OP_MULSUB;
     case OP_FROM_MONT: return OP_TO_MONT;
     case OP_TO_MONT: return OP_FROM_MONT;
+    case OP_INV: return OP_POW;
+    case OP_POW: return OP_INV;
     case OP_P_ADD_MIXED: case OP_P_ADD: return OP_P_DBL;
     }
     return -1;
@@ -91,9 +104,9 @@ template <class F> constexpr bool supported(int op) {
     if (op < 0 || op >= OP_COUNT) return false;
     if (op == OP_DOT4) return !Tr<F>::lazy && !Tr<F>::fq2;
     if (op == OP_CANON) return Tr<F>::lazy;
-    if (op == OP_FROM_MONT || op == OP_TO_MONT) return !Tr<F>::fq2;
-    if (op == OP_P_TO_AFFINE) return Tr<F>::points && !Tr<F>::lazy;
-    if (op >= OP_P_ADD_MIXED) return Tr<F>::points;
+    if (op == OP_FROM_MONT || op == OP_TO_MONT || op == OP_POW || op == OP_POW_U64 || op == OP_FROM_U64) return !Tr<F>::fq2;   // Fq2T has none of these
+    if (op == OP_P_TO_AFFINE || op == OP_P_MUL_SCALAR || op == OP_P_MUL_AFFINE_BITS) return Tr<F>::points && !Tr<F>::lazy;
+    if (op >= OP_P_ADD_MIXED && op <= OP_P_TO_AFFINE) return Tr<F>::points;
     return true;
 }
 template <class F> constexpr bool supported(int op, int mode) {
@@ -118,6 +131,10 @@ template <class P, bool INL> __device__ __forceinline__ void store(uint32_t *p, 
 template <class B> __device__ __forceinline__ void store(uint32_t *p, const Fq2T<B> &x) { store(p, x.c0); store(p + 8, x.c1); }
 template <class P, bool INL> __device__ __forceinline__ uint32_t limb0(const Fp<P, INL> &x) { return x.v[0]; }
 template <class B> __device__ __forceinline__ uint32_t limb0(const Fq2T<B> &x) { return x.c0.v[0]; }
+// the first 8 words of an element, for the operands that are raw words
+template <class P, bool INL> __device__ __forceinline__ const uint32_t *raw(const Fp<P, INL> &x) { return x.v; }
+template <class B> __device__ __forceinline__ const uint32_t *raw(const Fq2T<B> &x) { return x.c0.v; }
+__device__ __forceinline__ uint64_t raw64(const uint32_t *w) { return (uint64_t)w[1] << 32 | w[0]; }
 template <class P, bool INL> __device__ __forceinline__ void set_flag(Fp<P, INL> &x, bool b) { x = Fp<P, INL>::zero(); x.v[0] = b ? 1u : 0u; }
 template <class B> __device__ __forceinline__ void set_flag(Fq2T<B> &x, bool b) { x = Fq2T<B>::zero(); x.c0.v[0] = b ? 1u : 0u; }
 
@@ -150,6 +167,19 @@ __device__ __forceinline__ void apply(F *a, F *r) {
     else if constexpr (OP == OP_CANON) r[0] = canon_roundtrip(a[0]);
     else if constexpr (OP == OP_FROM_MONT) r[0] = F::from_mont(a[0]);
     else if constexpr (OP == OP_TO_MONT) r[0] = F::to_mont(a[0]);
+    else if constexpr (OP == OP_INV) r[0] = F::inv(a[0]);
+    else if constexpr (OP == OP_POW) r[0] = F::pow(a[0], raw(a[1]));
+    else if constexpr (OP == OP_POW_U64) r[0] = F::pow_u64(a[0], raw64(raw(a[1])));
+    else if constexpr (OP == OP_FROM_U64) r[0] = F::from_u64(raw64(raw(a[0])));
+    else if constexpr (OP == OP_P_MUL_SCALAR) {
+        const Xyzz<F> m = Xyzz<F>::mul_scalar(Xyzz<F>{a[0], a[1], a[2], a[3]}, raw(a[4]));
+        r[0] = m.x; r[1] = m.y; r[2] = m.zz; r[3] = m.zzz;
+    }
+    else if constexpr (OP == OP_P_MUL_AFFINE_BITS) {
+        const uint32_t *k = raw(a[2]);
+        const Xyzz<F> m = Xyzz<F>::mul_affine_bits(Affine<F>{a[0], a[1]}, raw64(k), raw64(k + 2), k[4] < 128 ? (int)k[4] : 128);
+        r[0] = m.x; r[1] = m.y; r[2] = m.zz; r[3] = m.zzz;
+    }
     else if constexpr (OP == OP_P_ADD_MIXED || OP == OP_P_ADD_MIXED_NZ) {
         Xyzz<F> acc{a[0], a[1], a[2], a[3]};
         const Affine<F> q{a[4], a[5]};
@@ -204,15 +234,6 @@ __global__ void __launch_bounds__(256) ft_kernel(const uint32_t *__restrict__ in
 #endif
 }
 
-char g_err[512] = "";
-bool g_failed = false;      // after a HIP error nothing more is launched
-
-int fail(int code, const char *what, const char *detail) {
-    snprintf(g_err, sizeof g_err, "%s: %s", what, detail);
-    if (code == FT_HIP_ERROR) g_failed = true;
-    return code;
-}
-
 template <class F, int OPA, int OPB, int MODE>
 int launch(const void *in, size_t operands, void *out, size_t results, size_t n) {
     constexpr int W = Tr<F>::words, NI = imax(nin_of(OPA), nin_of(OPB)), NO = imax(nout_of(OPA), nout_of(OPB));
@@ -222,25 +243,9 @@ int launch(const void *in, size_t operands, void *out, size_t results, size_t n)
         return fail(FT_BAD_ARGUMENT, "ft_run", d);
     }
     if (n == 0 || n > (size_t)1 << 24) return fail(FT_BAD_ARGUMENT, "ft_run", "n out of range");
-    const size_t bin = n * NI * W * 4, bout = n * NO * W * 4;
-    uint32_t *din = nullptr, *dout = nullptr;
-    hipError_t e = hipSetDevice(0);
-    const char *step = "hipSetDevice";
-    if (e == hipSuccess) { step = "hipMalloc"; e = hipMalloc((void **)&din, bin); }
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, bout);
-    if (e == hipSuccess) { step = "hipMemcpy (to device)"; e = hipMemcpy(din, in, bin, hipMemcpyHostToDevice); }
-    if (e == hipSuccess) { step = "hipMemset"; e = hipMemset(dout, 0xee, bout); }     // a result nobody wrote is not a valid one
-    if (e == hipSuccess) {
-        step = "kernel launch";
+    return device_run(in, n * NI * W * 4, out, n * NO * W * 4, [n](uint32_t *din, uint32_t *dout) {
         ft_kernel<F, OPA, OPB, MODE><<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(din, dout, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) { step = "hipDeviceSynchronize"; e = hipDeviceSynchronize(); }
-    if (e == hipSuccess) { step = "hipMemcpy (to host)"; e = hipMemcpy(out, dout, bout, hipMemcpyDeviceToHost); }
-    if (e != hipSuccess) return fail(FT_HIP_ERROR, step, hipGetErrorString(e));     // the buffers are left alone after an error
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    return FT_OK;
+    });
 }
 
 template <class F, int OP>
@@ -253,8 +258,9 @@ int run_op(int mode, const void *in, size_t operands, void *out, size_t results,
 
 #define FT_OPS(X) \
     X(OP_ADD) X(OP_SUB) X(OP_DBL) X(OP_NEG) X(OP_ADD2) X(OP_SUB2) X(OP_ADDSUB2) X(OP_MUL) X(OP_SQR) X(OP_MUL2) X(OP_SQR2) X(OP_MULSUB) X(OP_DOT4) \
-    X(OP_IS_ZERO) X(OP_EQ) X(OP_CANON) X(OP_FROM_MONT) X(OP_TO_MONT) \
-    X(OP_P_ADD_MIXED) X(OP_P_ADD_MIXED_NZ) X(OP_P_ADD) X(OP_P_DBL) X(OP_P_DBL_AFFINE) X(OP_P_NEG_IF) X(OP_P_TO_AFFINE)
+    X(OP_IS_ZERO) X(OP_EQ) X(OP_CANON) X(OP_FROM_MONT) X(OP_TO_MONT) X(OP_INV) X(OP_POW) X(OP_POW_U64) X(OP_FROM_U64) \
+    X(OP_P_ADD_MIXED) X(OP_P_ADD_MIXED_NZ) X(OP_P_ADD) X(OP_P_DBL) X(OP_P_DBL_AFFINE) X(OP_P_NEG_IF) X(OP_P_TO_AFFINE) \
+    X(OP_P_MUL_SCALAR) X(OP_P_MUL_AFFINE_BITS)
 
 template <class F>
 int run_type(int op, int mode, const void *in, size_t operands, void *out, size_t results, size_t n) {
@@ -269,6 +275,16 @@ int run_type(int op, int mode, const void *in, size_t operands, void *out, size_
 #define FT_TYPES(X) X(T_FQ, Fq) X(T_FQL, FqL) X(T_FQC, FqC) X(T_FR, Fr) X(T_FRL, FrL) X(T_FQ2, Fq2) X(T_FQ2L, Fq2T<FqL>) X(T_FQ2C, Fq2C)
 
 }  // namespace
+
+namespace ft {
+char g_err[512] = "";
+bool g_failed = false;
+int fail(int code, const char *what, const char *detail) {
+    snprintf(g_err, sizeof g_err, "%s: %s", what, detail);
+    if (code == FT_HIP_ERROR) g_failed = true;
+    return code;
+}
+}  // namespace ft
 
 extern "C" {
 

@@ -1,11 +1,13 @@
-"""Support shared by test_gpu_field_ops.py and test_gpu_point_ops.py: the ctypes binding of the test-only device library
-libfawkes_fieldtest.so (csrc/fieldtest.hip), its type / operation / mode tables, and the limb encoding.
+"""Support shared by test_gpu_field_ops.py, test_gpu_point_ops.py and the tower tests (_tower_cases.py): the ctypes binding of the
+test-only library libfawkes_fieldtest.so (csrc/fieldtest.hip, csrc/fieldtest_tower.hip), its type / operation / mode tables, the limb
+encoding and the generators of edge and structured limb images.
 
 Values are Python integers throughout: an element of a base field is an int, an element of an Fq2 type is a pair (c0, c1).  What
 goes to the device and comes back is the Montgomery limb image itself (8 x u32 little endian = 32 bytes little endian), not a
 value converted on the way: the tests choose the limbs.
 """
 import ctypes as C
+import functools
 import os
 
 import pytest
@@ -36,9 +38,16 @@ TYPES = [Type('Fq', 0, P_FQ), Type('FqL', 1, P_FQ, lazy=True), Type('FqC', 2, P_
 TYPE = {t.name: t for t in TYPES}
 OP_NAMES = ['add', 'sub', 'dbl', 'neg', 'add2', 'sub2', 'addsub2', 'mul', 'sqr', 'mul2', 'sqr2', 'mulsub', 'dot4',
             'is_zero', 'eq', 'canon', 'from_mont', 'to_mont',
-            'p_add_mixed', 'p_add_mixed_nz', 'p_add', 'p_dbl', 'p_dbl_affine', 'p_neg_if', 'p_to_affine']
+            'p_add_mixed', 'p_add_mixed_nz', 'p_add', 'p_dbl', 'p_dbl_affine', 'p_neg_if', 'p_to_affine',
+            'inv', 'pow', 'pow_u64', 'from_u64', 'p_mul_scalar', 'p_mul_affine_bits']      # ids stay: new operations go to the end
 OP = {n: i for i, n in enumerate(OP_NAMES)}
 MODE = {'straight': 0, 'divergent': 1, 'aliased': 2}
+# ids as in csrc/fieldtest_tower.hip
+TOWER_OPS = ['f6_mul', 'f6_mul_by_01', 'f6_mul_by_fq2', 'f6_mul_v', 'f6_mul_xi', 'f6_inv', 'f6_add', 'f6_sub', 'f6_neg',
+             'f12_mul', 'f12_sqr_complex', 'f12_mul_by_line', 'f12_conj', 'f12_inv', 'f12_is_one', 'f12_pow',
+             'miller_loop', 'miller_loop_proj', 'final_exp']
+TOWER_OP = {n: i for i, n in enumerate(TOWER_OPS)}
+WHERE = {'device': 0, 'host': 1}
 
 
 class FieldTestLib:
@@ -57,6 +66,9 @@ class FieldTestLib:
             lib.ft_run.restype = C.c_int
             lib.ft_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t]
             lib.ft_supported.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            lib.ft_tower_shape.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            lib.ft_tower_run.restype = C.c_int
+            lib.ft_tower_run.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t]
             self._lib = lib
         return self._lib
 
@@ -95,6 +107,67 @@ class FieldTestLib:
         if t.fq2:
             vals = list(zip(vals[0::2], vals[1::2]))
         return [tuple(vals[i * no:(i + 1) * no]) for i in range(n)]
+
+
+    def tower_shape(self, op_id):
+        """(words in, words out) of one case of a tower operation, or None"""
+        wi, wo = C.c_int(0), C.c_int(0)
+        if not self.lib().ft_tower_shape(op_id, C.byref(wi), C.byref(wo)):
+            return None
+        return wi.value, wo.value
+
+    def run_tower(self, op, where, cases):
+        """cases: a list of byte strings, each the words of one case -> the list of the cases' result bytes"""
+        if self.failed:
+            pytest.fail('not launched: an earlier call of this module failed (%s)' % self.failed)
+        wi, wo = self.tower_shape(TOWER_OP[op])
+        n = len(cases)
+        assert n and all(len(c) == 4 * wi for c in cases), (op, wi, [len(c) for c in cases][:4])
+        out = C.create_string_buffer(n * wo * 4)
+        rc = self.lib().ft_tower_run(TOWER_OP[op], WHERE[where], b''.join(cases), wi, out, wo, n)
+        if rc != 0:
+            self.failed = 'ft_tower_run(%s, %s) returned %d: %s' % (op, where, rc, (self.lib().ft_last_error() or b'').decode())
+            pytest.fail(self.failed)
+        key = (where, op, 'tower')
+        self.cases_run[key] = self.cases_run.get(key, 0) + n
+        raw = out.raw
+        return [raw[i * wo * 4:(i + 1) * wo * 4] for i in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------ limb images worth trying
+LIMB_PICKS = (0, 1, 0x7fffffff, 0x80000000, 0xfffffffe, 0xffffffff)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_list(p, lazy):
+    q = 2 * p if lazy else p
+    r = MONT_R % p
+    vals = [0, 1, 2, p - 1, p, p + 1, 2 * p - 1, q - 1, r, r * r % p]
+    if lazy:
+        vals += [r + p, r * r % p + p]
+    for k in (31, 32, 33, 63, 64, 224, 253):
+        vals += [1 << k, (1 << k) - 1]
+    vals += [0xffffffff << (32 * i) for i in range(8)]
+    vals.append(sum(0x80000000 << (32 * i) for i in range(8)))
+    qtop, out = q >> 224, []
+    for v in vals:
+        if v >= q:                  # clipped: the low seven limbs stay, the top limb comes under q's
+            v = (v & ((1 << 224) - 1)) | (min(v >> 224, qtop - 1) << 224)
+        assert 0 <= v < q
+        if v not in out:
+            out.append(v)
+    return tuple(out)
+
+
+def structured(rnd, q):
+    qtop = q >> 224
+    v = 0
+    for i in range(7):
+        k = rnd.randrange(7)
+        v |= (LIMB_PICKS[k] if k < 6 else rnd.getrandbits(32)) << (32 * i)
+    tops = [x for x in LIMB_PICKS if x < qtop]
+    k = rnd.randrange(len(tops) + 1)
+    return v | ((tops[k] if k < len(tops) else rnd.randrange(qtop)) << 224)
 
 
 def first_limb_odd(t, element):

@@ -19,6 +19,10 @@ Operands (lazy types draw from all of [0, 2p), both representatives x and x + p 
   uniform    a few hundred, the common case
 Random 254-bit operands reach none of the first three: a limb of 0 or 0xffffffff, a sum on q, a reduction ending at p.
 
+inv, pow, pow_u64, from_u64 (and Fq2T::inv) are the loops everything above the field is built on (to_affine, the slopes of the Miller
+loop, the final exponentiation): inv against a^-1 R^2 (0 -> 0, the Fermat value, pinned), pow against Python's pow.  The exponent
+of pow, and the 64-bit argument of pow_u64 / from_u64, are raw words in an element's place, not range-limited (RAW).
+
 Modes (csrc/fieldtest.hip): straight with a partial last wave; divergent (odd first operands run the operation, the others a
 different one, both checked); aliased (outputs written over inputs by the call).
 
@@ -31,13 +35,12 @@ import random
 
 import pytest
 
-from _fieldtest import MONT_R, TYPES, FieldTestLib, check_element, first_limb_odd, hexel
+from _fieldtest import MONT_R, TYPES, FieldTestLib, check_element, edge_list, first_limb_odd, hexel, structured
 
 pytestmark = pytest.mark.gpu
 
 LIB = FieldTestLib()        # the module-level guard: after one failed call nothing more is launched from this module
 
-LIMB_PICKS = (0, 1, 0x7fffffff, 0x80000000, 0xfffffffe, 0xffffffff)
 N_STRUCTURED, N_UNIFORM = 4000, 300
 
 
@@ -67,6 +70,25 @@ def is_zero(t, a):
     return all(v % t.p == 0 for v in a) if t.fq2 else a % t.p == 0
 
 
+def _inv(t, v):
+    return pow(v, -1, t.p) if v % t.p else 0          # Fermat: 0^(p - 2) = 0
+
+
+def inv(t, a):
+    """the image of 1 / x for the image a of x: a^-1 R^2; in Fq2, conj(a) R^2 / (a0^2 + a1^2)"""
+    if t.fq2:
+        n = _inv(t, a[0] * a[0] + a[1] * a[1]) * MONT_R * MONT_R
+        return (a[0] * n, -a[1] * n)
+    return _inv(t, a) * MONT_R * MONT_R
+
+
+def power(t, a, e):
+    return pow(a * t.rinv % t.p, e, t.p) * MONT_R
+
+
+U64 = (1 << 64) - 1
+
+
 def flag(t, b):
     return (int(b), 0) if t.fq2 else int(b)
 
@@ -91,7 +113,12 @@ REF = {
     'canon': (1, 1, True, lambda t, a: (a[0],)),                       # canon() then lazy_of(): the canonical limbs of the same residue
     'from_mont': (1, 1, False, lambda t, a: (a[0] * t.rinv,)),
     'to_mont': (1, 1, False, lambda t, a: (a[0] * MONT_R,)),
+    'inv': (1, 1, False, lambda t, a: (inv(t, a[0]),)),
+    'pow': (2, 1, False, lambda t, a: (power(t, a[0], a[1]),)),
+    'pow_u64': (2, 1, False, lambda t, a: (power(t, a[0], a[1] & U64),)),
+    'from_u64': (1, 1, False, lambda t, a: ((a[0] & U64) * MONT_R,)),
 }
+RAW = {'pow': (1,), 'pow_u64': (1,), 'from_u64': (0,)}       # operands that are raw words: any 256-bit value may stand there
 FIELD_OPS = list(REF)
 
 
@@ -101,14 +128,14 @@ def has(t, op):
         return not t.lazy and not t.fq2
     if op == 'canon':
         return t.lazy
-    if op in ('from_mont', 'to_mont'):
+    if op in ('from_mont', 'to_mont', 'pow', 'pow_u64', 'from_u64'):        # Fq2T has none of these; Fq2T::inv it has
         return not t.fq2
     return True
 
 
 DIVERGENT_ALT = {'add': 'mul', 'sub': 'add', 'dbl': 'neg', 'neg': 'sqr', 'mul': 'sub', 'sqr': 'dbl', 'add2': 'sqr2', 'sub2': 'add2',
                  'addsub2': 'mul2', 'mul2': 'addsub2', 'sqr2': 'sub2', 'mulsub': 'mul2', 'dot4': 'mulsub', 'from_mont': 'to_mont',
-                 'to_mont': 'from_mont'}
+                 'to_mont': 'from_mont', 'inv': 'pow', 'pow': 'inv'}
 ALIASED = ('add', 'sub', 'dbl', 'mul', 'sqr', 'mulsub', 'add2', 'sub2', 'addsub2', 'mul2', 'sqr2')
 
 
@@ -120,38 +147,6 @@ COMBOS = [(t, op, mode) for t in TYPES for op in FIELD_OPS if has(t, op) for mod
 
 
 # ------------------------------------------------------------------------------------------------ operands
-@functools.lru_cache(maxsize=None)
-def edge_list(p, lazy):
-    q = 2 * p if lazy else p
-    r = MONT_R % p
-    vals = [0, 1, 2, p - 1, p, p + 1, 2 * p - 1, q - 1, r, r * r % p]
-    if lazy:
-        vals += [r + p, r * r % p + p]
-    for k in (31, 32, 33, 63, 64, 224, 253):
-        vals += [1 << k, (1 << k) - 1]
-    vals += [0xffffffff << (32 * i) for i in range(8)]
-    vals.append(sum(0x80000000 << (32 * i) for i in range(8)))
-    qtop, out = q >> 224, []
-    for v in vals:
-        if v >= q:                  # clipped: the low seven limbs stay, the top limb comes under q's
-            v = (v & ((1 << 224) - 1)) | (min(v >> 224, qtop - 1) << 224)
-        assert 0 <= v < q
-        if v not in out:
-            out.append(v)
-    return tuple(out)
-
-
-def structured(rnd, q):
-    qtop = q >> 224
-    v = 0
-    for i in range(7):
-        k = rnd.randrange(7)
-        v |= (LIMB_PICKS[k] if k < 6 else rnd.getrandbits(32)) << (32 * i)
-    tops = [x for x in LIMB_PICKS if x < qtop]
-    k = rnd.randrange(len(tops) + 1)
-    return v | ((tops[k] if k < len(tops) else rnd.randrange(qtop)) << 224)
-
-
 def lifts(p, lazy, x):
     return [x, x + p] if lazy and x < p else [x]
 
@@ -251,6 +246,36 @@ def t_dbl(p, lazy):
     return tuple((v,) for v in vals if v < q)
 
 
+@functools.lru_cache(maxsize=None)
+def t_inv(p, lazy):
+    """images 0, 1, p - 1, R, 1 / 2, and those whose inverse's image is 1, p - 1 or R; in a lazy type both representatives"""
+    r = MONT_R % p
+    vals = [0, 1, p - 1, r, (p + 1) // 2, r * r % p, -r * r % p, (p + 1) // 2 * r % p]
+    return tuple((y,) for x in vals for y in lifts(p, lazy, x))
+
+
+@functools.lru_cache(maxsize=None)
+def t_pow(p, lazy):
+    """(a, e): e in 0, 1, 2, p - 2, (p - 1) / 2, 2^256 - 1, 2^255, and with zero high words; a = 0 among the bases"""
+    rnd, q = random.Random(17), 2 * p if lazy else p
+    es = [0, 1, 2, p - 2, (p - 1) // 2, (1 << 256) - 1, 1 << 255, p, 2 * p + 1] + [rnd.getrandbits(k) | 1 << (k - 1) for k in (31, 32, 33, 64, 96, 128, 224)]
+    bases = [0, 1, p - 1, MONT_R % p] + [_nonzero(rnd, p, q) for _ in range(4)] + ([p, p + 1] if lazy else [])
+    return tuple((a, e) for e in es for a in bases)
+
+
+@functools.lru_cache(maxsize=None)
+def t_pow_u64(p, lazy):
+    """(a, e): e in 0, 1, 2^63, 2^64 - 1, alone and under words the method must not see"""
+    rnd, q = random.Random(18), 2 * p if lazy else p
+    es = [0, 1, 2, 1 << 63, U64, 1 << 32, (1 << 32) - 1]
+    es += [e | rnd.getrandbits(192) << 64 for e in es]
+    return tuple((a, e) for e in es for a in (0, MONT_R % p, _nonzero(rnd, p, q), _nonzero(rnd, p, q)))
+
+
+def t_from_u64(p, lazy):
+    return tuple((x | hi << 64,) for x in (0, 1, 1 << 32, U64, 1 << 63, (1 << 32) - 1) for hi in (0, 1, (1 << 192) - 1))
+
+
 def _rot(xs, k):
     k %= len(xs)
     return xs[k:] + xs[:k]
@@ -304,7 +329,8 @@ def targeted(t, op):
     p, lazy = t.p, t.lazy
     pair2 = lambda xs, ys: [x + y for x, y in zip(xs, _rot(ys, 5))] + [x + y for x, y in zip(_rot(ys, 3), xs)]
     if not t.fq2:
-        base = {'add': t_add, 'sub': t_sub, 'eq': t_sub, 'dbl': t_dbl, 'mul': t_mul, 'mulsub': t_mulsub}
+        base = {'add': t_add, 'sub': t_sub, 'eq': t_sub, 'dbl': t_dbl, 'mul': t_mul, 'mulsub': t_mulsub,
+                'inv': t_inv, 'pow': t_pow, 'pow_u64': t_pow_u64, 'from_u64': t_from_u64}
         if op in base:
             return list(base[op](p, lazy))
         if op == 'add2':
@@ -330,6 +356,9 @@ def targeted(t, op):
         return pair2(t_fq2mul(p, lazy), t_fq2mul(p, lazy))
     if op == 'mulsub':
         return list(t_fq2mulsub(p, lazy))
+    if op == 'inv':         # norm zero only at 0; pure real, pure imaginary, and every pair of the base targets
+        xs = [x for x, in t_inv(p, lazy)]
+        return [(x, y) for x in xs for y in xs]
     return []
 
 
@@ -341,7 +370,7 @@ def cases_for(t, op, operands):
     flat, labels = [c for c, _ in gen], [l for _, l in gen]
     e = edge_list(t.p, t.lazy)
     for i, c in enumerate(targeted(t, op)):
-        assert len(c) == REF[op][0] * t.w and all(0 <= v < t.q for v in c), (op, c)
+        assert len(c) == REF[op][0] * t.w and all(0 <= v < (MONT_R if j in RAW.get(op, ()) else t.q) for j, v in enumerate(c)), (op, c)
         flat.append(tuple(c) + tuple(e[(i + 5 * m) % len(e)] for m in range(k - len(c))))
         labels.append('targeted')
     if len(flat) % 64 == 0:         # the last wave is partial

@@ -4,7 +4,8 @@ Each formula is called directly by a thin kernel of the test-only library (csrc/
 product instantiates it with: Fq, FqL, FqC (G1) and Fq2, Fq2T<FqL>, Fq2C (G2).  The XYZZ result the device returns is brought to
 affine form in Python (x = X / ZZ, y = Y / ZZZ, infinity if and only if ZZ is zero) and compared with the reference; every result
 also satisfies ZZ^3 == ZZZ^2 and the range of its type ([0, p), lazy [0, 2p)).  to_affine and affine_neg_if are compared as field
-values (canonical types bit for bit).
+values (canonical types bit for bit).  The two scalar multiplications, mul_scalar (the subgroup check of B in the verifiers: r B must
+be infinity) and mul_affine_bits (w A and w C of the aggregate verifier), are compared with `G.mul` over the non-lazy types.
 
 Accumulators are fed in non-trivial XYZZ form, (x l^2, y l^3, l^2, l^3) for a random l; in the lazy types every coordinate is
 randomly lifted by p.  Exceptional cases, in every type: accumulator at infinity, addend at infinity (the all-zero buffer, and in a
@@ -163,8 +164,8 @@ def group_expect(t):
 
 def test_library_offers_the_point_kernels():
     for t in TYPES:
-        for op in ('p_add_mixed', 'p_add_mixed_nz', 'p_add', 'p_dbl', 'p_dbl_affine', 'p_neg_if', 'p_to_affine'):
-            want = t.points and (op != 'p_to_affine' or not t.lazy)
+        for op in ('p_add_mixed', 'p_add_mixed_nz', 'p_add', 'p_dbl', 'p_dbl_affine', 'p_neg_if', 'p_to_affine', 'p_mul_scalar', 'p_mul_affine_bits'):
+            want = t.points and (op not in ('p_to_affine', 'p_mul_scalar', 'p_mul_affine_bits') or not t.lazy)
             assert (LIB.shape(t, op, 'straight') is not None) == want, (t, op)
     assert LIB.alt('p_add_mixed') == 'p_dbl' and LIB.alt('p_add') == 'p_dbl'
 
@@ -199,6 +200,58 @@ def test_point_dbl_affine(t):
     for lift in ((0, 1) if t.lazy else (0,)):
         cases += [(e.affine(pts[i], lift), pts[i], None, 'wholly lifted %d' % lift) for i in range(4)]
     run_points(t, 'p_dbl_affine', 'straight', cases, group_expect(t))
+
+
+MUL_TYPES = [t for t in POINT_TYPES if not t.lazy]      # the product multiplies in Fq, FqC (G1) and Fq2, Fq2C (G2) only
+R_ORDER = ref.R
+
+
+def raw_el(t, k):
+    """raw words in an element's place (csrc/fieldtest.hip): the first 8 words of the element"""
+    return (k, 0) if t.fq2 else k
+
+
+@pytest.mark.parametrize('t', MUL_TYPES, ids=str)
+def test_point_mul_scalar(t):
+    """Xyzz::mul_scalar(p, k) == k p for any 256-bit k.  k = r gives infinity: this call is the subgroup check of B in the verifiers
+    (verify.hip, verify_agg.hip, keyfile.hip)."""
+    assert LIB.shape(t, 'p_mul_scalar', 'straight') == (5, 4)
+    G, _ = curve(t)
+    e = Enc(t, 71 + t.id)
+    pts, rnd = base_points(t.fq2), random.Random(72 + t.id)
+    special = [0, 1, 2, 3, R_ORDER - 1, R_ORDER, R_ORDER + 1, (1 << 256) - 1, 1 << 255, 1 << 32, (1 << 32) - 1, 2 * R_ORDER]
+    cases = []
+    for i, k in enumerate(special):
+        for j in range(2):
+            pt = pts[(2 * i + j) % len(pts)]
+            cases.append((e.xyzz(pt) + (raw_el(t, k),), pt, k, 'k = %#x' % k))
+            cases.append(((e.el(pt[0]), e.el(pt[1]), e.el(e.F.one), e.el(e.F.one), raw_el(t, k)), pt, k, 'k = %#x, ZZ = ZZZ = 1' % k))
+        cases.append((e.xyzz(None, junk=bool(i & 1)) + (raw_el(t, k),), None, k, 'infinity, k = %#x' % k))
+    for i in range(24 if t.fq2 else 40):
+        pt, k = pts[rnd.randrange(len(pts))], rnd.getrandbits(rnd.choice((256, 254, 128, 64)))
+        cases.append((e.xyzz(pt) + (raw_el(t, k),), pt, k, 'random'))
+    assert all(G.mul(p, R_ORDER) is None for p in pts[:4])
+    run_points(t, 'p_mul_scalar', 'straight', cases, lambda which, a, k: G.mul(a, k))
+
+
+@pytest.mark.parametrize('t', MUL_TYPES, ids=str)
+def test_point_mul_affine_bits(t):
+    """Xyzz::mul_affine_bits(p, lo, hi, nbits) == (hi 2^64 + lo) p: w A and w C of the aggregate verifier, the ceremony's random
+    combinations.  The product calls it with nbits = 128 only; 64 is the other width its contract names (k below 2^nbits)."""
+    assert LIB.shape(t, 'p_mul_affine_bits', 'straight') == (3, 4)
+    G, _ = curve(t)
+    e = Enc(t, 81 + t.id)
+    pts, rnd = base_points(t.fq2), random.Random(82 + t.id)
+    m64 = (1 << 64) - 1
+    ks = [(1, 0, 128), (0, 1, 128), (m64, m64, 128), (0, 0, 128), (0, 1 << 63, 128), (m64, 0, 128), (2, 0, 128), (1, 0, 64), (m64, 0, 64), (1 << 63, 0, 64)]
+    ks += [(rnd.getrandbits(64), rnd.getrandbits(64), 128) for _ in range(16 if t.fq2 else 30)] + [(rnd.getrandbits(64), 0, 64) for _ in range(4)]
+    cases = []
+    for i, (lo, hi, nbits) in enumerate(ks):
+        pt, kel = pts[i % len(pts)], raw_el(t, lo | hi << 64 | nbits << 128)
+        cases.append((e.affine(pt) + (kel,), pt, hi << 64 | lo, 'lo %#x hi %#x nbits %d' % (lo, hi, nbits)))
+        if i < 10:
+            cases.append((e.affine(None) + (kel,), None, hi << 64 | lo, 'infinity, lo %#x hi %#x nbits %d' % (lo, hi, nbits)))
+    run_points(t, 'p_mul_affine_bits', 'straight', cases, lambda which, a, k: G.mul(a, k))
 
 
 @pytest.mark.parametrize('t', POINT_TYPES, ids=str)
