@@ -32,3 +32,8 @@ from . import ceremony_init  # noqa: F401
 from .ceremony_init import (  # noqa: F401
     PowersOfTau, PowersReport, g1_ntt, g2_ntt, initial_key, initial_key_host, initial_image, check_powers, check_powers_host,
 )
+from . import powers  # noqa: F401
+from .powers import (  # noqa: F401
+    PowersPublic, PointsReport, PowersUpdateReport, new_powers, contribute, contribute_host, scale_powers, scale_powers_dev, validate_points,
+    check_update, check_update_host,
+)

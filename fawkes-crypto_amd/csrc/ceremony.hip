@@ -12,52 +12,7 @@
 namespace fk {
 
 // ------------------------------------------------------------------------------------------ one scalar, many points
-// The scalar in non-adjacent form: digit i in {-1, 0, 1}, no two neighbours nonzero, at most 255 digits for k < r and a third of them
-// nonzero.  `n` digits, the top one (always +1) dropped, the rest moved up so that digit n - 2 is bit 255 of its mask: the kernel walks
-// the masks by shifting them left, as Xyzz::mul_affine_bits walks its scalar -- a run-time index into an array of words would put the
-// array into scratch (witness.hip and poseidon.hip met that).  Passed by value: the masks live in scalar registers and every branch on a
-// digit is wave-uniform.
-struct NafDigits { uint64_t pos[4], neg[4]; uint32_t n; };
-
-static NafDigits naf_recode(const Fr &k_canon) {
-    uint64_t k[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < 4; i++) k[i] = (uint64_t)k_canon.v[2 * i] | (uint64_t)k_canon.v[2 * i + 1] << 32;
-    NafDigits d;
-    memset(&d, 0, sizeof d);
-    uint32_t i = 0;
-    while (k[0] | k[1] | k[2] | k[3] | k[4]) {
-        if (k[0] & 1) {
-            if ((k[0] & 3) == 1) { d.pos[i >> 6] |= (uint64_t)1 << (i & 63); k[0] -= 1; }          // (odd: no borrow)
-            else { d.neg[i >> 6] |= (uint64_t)1 << (i & 63); for (int j = 0; j < 5 && ++k[j] == 0; j++) {} }
-        }
-        for (int j = 0; j < 4; j++) k[j] = k[j] >> 1 | k[j + 1] << 63;
-        k[4] >>= 1;
-        i++;
-    }
-    d.n = i;
-    if (i == 0) return d;
-    d.pos[(i - 1) >> 6] &= ~((uint64_t)1 << ((i - 1) & 63));          // the top digit is implied
-    for (uint32_t s = 256 - (i - 1); s > 0; s--) {                   // (host, once per call)
-        for (int j = 3; j > 0; j--) { d.pos[j] = d.pos[j] << 1 | d.pos[j - 1] >> 63; d.neg[j] = d.neg[j] << 1 | d.neg[j - 1] >> 63; }
-        d.pos[0] <<= 1; d.neg[0] <<= 1;
-    }
-    return d;
-}
-
-// k * p for an affine p that is not the point at infinity and k.n >= 1: k.n - 1 doublings, one mixed addition of +-p per nonzero digit
-template <class F>
-static FK_HD Xyzz<F> mul_naf(const Affine<F> &p, NafDigits k) {
-    Xyzz<F> acc{p.x, p.y, F::one(), F::one()};
-    for (uint32_t left = k.n; left > 1; left--) {
-        acc = Xyzz<F>::dbl(acc);
-        const bool plus = k.pos[3] >> 63, minus = k.neg[3] >> 63;
-        if (plus || minus) acc.add_mixed_nz(affine_neg_if(p, minus));
-        for (int j = 3; j > 0; j--) { k.pos[j] = k.pos[j] << 1 | k.pos[j - 1] >> 63; k.neg[j] = k.neg[j] << 1 | k.neg[j - 1] >> 63; }
-        k.pos[0] <<= 1; k.neg[0] <<= 1;
-    }
-    return acc;
-}
-
+// (NafDigits, naf_recode and mul_naf live in ceremony_shared.hpp: powers.hip walks r with them)
 // One point per lane.  A lane whose input is the point at infinity runs the loop on the generator and stores infinity: it stays in step
 // with its wave instead of making all 64 lanes wait for two paths through ~340 group operations.  in == out is allowed (a lane reads its
 // own element before it writes it), hence no __restrict__.

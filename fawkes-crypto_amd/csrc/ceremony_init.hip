@@ -22,19 +22,7 @@
 namespace fk {
 
 // ------------------------------------------------------------------------------------------ a point times the lane's own scalar
-// A canonical scalar as four 64-bit words, walked by shifting it left as Xyzz::mul_affine_bits walks its two: a run-time index into the
-// limbs (Xyzz::mul_scalar) would put the scalar into scratch on the device.
-struct K256 { uint64_t w[4]; };
-static FK_HD K256 k256_of_mont(const Fr &k_mont) {
-    const Fr c = Fr::from_mont(k_mont);
-    K256 k;
-    for (int i = 0; i < 4; i++) k.w[i] = (uint64_t)c.v[2 * i] | (uint64_t)c.v[2 * i + 1] << 32;
-    return k;
-}
-static FK_HD void k256_shl(K256 &k) {
-    k.w[3] = k.w[3] << 1 | k.w[2] >> 63; k.w[2] = k.w[2] << 1 | k.w[1] >> 63; k.w[1] = k.w[1] << 1 | k.w[0] >> 63; k.w[0] <<= 1;
-}
-
+// (K256, k256_of_mont, k256_shl and mul_affine_k256 live in ceremony_shared.hpp: powers.hip multiplies by a lane's own scalar too)
 // k * p, p in XYZZ form (a butterfly's operand): complete additions
 template <class F>
 static FK_HD Xyzz<F> mul_xyzz_k256(const Xyzz<F> &p, K256 k) {
@@ -47,19 +35,6 @@ static FK_HD Xyzz<F> mul_xyzz_k256(const Xyzz<F> &p, K256 k) {
     }
     return acc;
 }
-// k * p, p affine and not the point at infinity (a term of a combination): mixed additions
-template <class F>
-static FK_HD Xyzz<F> mul_affine_k256(const Affine<F> &p, K256 k) {
-    Xyzz<F> acc = Xyzz<F>::inf();
-#pragma nounroll
-    for (int i = 0; i < 256; i++) {
-        acc = Xyzz<F>::dbl(acc);
-        if (k.w[3] >> 63) acc.add_mixed_nz(p);
-        k256_shl(k);
-    }
-    return acc;
-}
-
 static FK_HD uint64_t bit_reverse(uint64_t i, uint32_t bits) {
     uint64_t r = 0;
     for (uint32_t b = 0; b < bits; b++) { r = r << 1 | (i & 1); i >>= 1; }

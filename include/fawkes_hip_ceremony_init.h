@@ -28,7 +28,8 @@
  * tau_g2[1] (of tau_g1[1] for ratio_tau_g2).  For an array that is not a geometric sequence with ratio tau this is a nonzero linear form in
  * the rho_i and vanishes with probability 2^-128 over the weights.  THE STATEMENT IS VOID FOR WEIGHTS THE TRANSCRIPT'S AUTHOR CAN PREDICT:
  * pass seed = NULL (32 bytes of getrandom(2) per call) outside tests, and never a seed that was known before the transcript was published.
- * The check and the derivation ASSUME every point is on its curve and in the order-r subgroup; neither is tested here.  A key derived
+ * The check and the derivation ASSUME every point is on its curve and in the order-r subgroup; neither is tested here
+ * (fk_points_validate and fk_powers_update_check of fawkes_hip_powers.h test both).  A key derived
  * from an inconsistent transcript is silently worthless: check first.
  *
  * Out of scope: tiled systems (copies > 1), sharded and multi-GPU keys (the key that comes out is whole, shard_count == 1), BGM17's
