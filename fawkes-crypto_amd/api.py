@@ -993,6 +993,13 @@ class Context(_Handle):
         out['tasks'], out['obs'] = tasks[:out['dyn']['n_tasks']], obs[:out['dyn']['n_obs']]
         return out
 
+    def msm_back_dump(self, entry, out, d_bases, d_scalars, n, g2=False, merged=False):
+        """The back of one multiplication over device-resident bases and scalars, stage by stage (include/fawkes_hip_inspect.h).  The entry
+        point is test-only and stays out of the prototype table: `entry` is the library's function with the prototype the caller declared,
+        `out` the caller's fk_msm_back_out, its buffers sized from msm_plan(n, the context's window bits, merged) (tests/_msm_back_ref.py)."""
+        self.set_window_bits(self._window_bits)      # the caller's buffers are sized from these bits: the library must not hold others
+        self._ck(entry(self.handle, int(g2), d_bases, d_scalars, n, int(merged), C.byref(out)))
+
     def gen_points_g1_dev(self, dptr, n, seed):
         self._ck(self.lib.fk_gen_points_g1_dev(self.handle, dptr, n, seed))
 

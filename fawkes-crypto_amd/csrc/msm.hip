@@ -28,6 +28,7 @@
 //                      kernel folds the workgroups' partial sums, the window sums are copied to pinned host memory.
 //   6. host            W window sums are Horner-combined (cw doublings each) -- microseconds.
 #include "common.hpp"
+#include "../../include/fawkes_hip_inspect.h"
 #include <algorithm>
 #include <string.h>
 #include <type_traits>
@@ -1481,6 +1482,20 @@ int msm_g2_dev(fk_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t
     return msm_run<Fq2>(ctx, d_bases, d_scalars, n, out, reuse_sort, pre);
 }
 
+// Queues the levels 1 .. W-1 of n bases under the merged plan p on the main stream: level w = 2^(width of window w-1) * level w-1, written
+// to lev + (w - 1) * n (level 0 is d_bases).  precompute_levels below (a key's arrays) and fk_msm_back_dump (tests) both build theirs here.
+template <class F>
+static void queue_levels(fk_ctx *ctx, const Affine<F> *d_bases, size_t n, const MsmPlan &p, Affine<F> *lev) {
+    const Affine<F> *prev = d_bases;
+    for (uint32_t w = 1; w < p.W; w++) {
+        Affine<F> *cur = lev + (size_t)(w - 1) * n;
+        const uint32_t bits = p.cb + ((w - 1) < p.wide ? 1 : 0);       // width of window w-1
+        constexpr int NB = sizeof(F) == sizeof(Fq) ? 4 : 2;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_level_kernel<F, NB>), dim3((unsigned)(((n + NB - 1) / NB + 255) / 256)), dim3(256), 0, ctx->stream, prev, n, bits, cur);
+        prev = cur;
+    }
+}
+
 // ------------------------------------------------------------------------------------------ inspection entry points (tests)
 // fk_msm_plan: the window plan of a multiplication of n points and the compile-time limits it is sized against.  Host only.
 static void msm_plan_info(size_t n, unsigned window_bits, bool merged, fk_msm_plan_info *out) {
@@ -1533,6 +1548,79 @@ static int msm_front_dump(fk_ctx *ctx, const Fr *d_scalars, size_t n, bool merge
     return FK_OK;
 }
 
+// fk_msm_back_dump: one whole multiplication, queued piece by piece through the host code a multiplication goes through (msm_reserve,
+// queue_sort, queue_size_order, queue_accumulate, queue_tail, msm_end) with the lane synchronised behind each piece, so that what the
+// accumulation, the oversized-bucket kernels, the bucket reduction and the fold left can be copied out beside the front's tables.  The
+// tail record is claimed only for msm_end, which releases it; the lane forgets the sort as in msm_front_dump.  merged: the levels are
+// built here (queue_levels) and freed when the call returns.
+template <class F>
+static int msm_back_dump(fk_ctx *ctx, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, bool merged, const fk_msm_back_out &o) {
+    if (n == 0) return FK_OK;
+    if (n >= ((size_t)1 << 31)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: n too large");
+    if (proof_holds_lanes(ctx)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm back dump: a proof is in flight on this context");
+    int ti = -1;
+    for (int i = 0; i < MSM_TAILS; i++) if (!ctx->tails[i].active) { ti = i; break; }
+    if (ti < 0) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "msm: too many outstanding multiplications");
+    MsmTail &tl = ctx->tails[ti];
+    if (!tl.done) FK_HIP(ctx, hipEventCreateWithFlags(&tl.done, hipEventDisableTiming));
+    const int li = ctx->lane_next;
+    MsmLane &ln = ctx->lanes[li];
+    if (!ln.st) FK_SET_ERR(ctx, FK_ERR_HIP, "msm: the context's streams were not created");
+    MsmJob<F> job{};
+    job.ctx = ctx; job.p = make_plan(n, ctx->window_bits, merged); job.ln = &ln; job.tl = &tl;
+    job.bases = d_bases; job.scalars = d_scalars; job.n = n; job.merged = merged;
+    const MsmPlan &p = job.p;
+    struct Levels { void *p = nullptr; ~Levels() { if (p) (void)hipFree(p); } } lev;
+    if (merged) {
+        const size_t bytes = (size_t)(p.W - 1) * n * sizeof(Affine<F>);
+        FK_HIP(ctx, hipMalloc(&lev.p, bytes ? bytes : 64));
+        queue_levels(ctx, d_bases, n, p, (Affine<F> *)lev.p);
+        FK_HIP(ctx, hipGetLastError());
+        FK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (o.levels && bytes) FK_HIP(ctx, hipMemcpy(o.levels, lev.p, bytes, hipMemcpyDeviceToHost));
+        job.lev = (const Affine<F> *)lev.p;
+    }
+    lanes_advance(ctx, li);
+    FK_HIP(ctx, hipEventRecord(ln.ev_in, ctx->stream));        // scalars and bases produced on the main stream
+    FK_HIP(ctx, hipStreamWaitEvent(ln.st, ln.ev_in, 0));
+    // ---- the front, as msm_front_dump
+    FK_TRY(msm_reserve(job));
+    FK_TRY(lane_reclaim(ctx, ln, /*host_wait=*/true));
+    FK_TRY(queue_sort(job));
+    FK_TRY(queue_size_order(job));
+    ln.last_sort_scalars = nullptr;
+    FK_HIP(ctx, hipStreamSynchronize(ln.st));
+    const size_t Wn = (size_t)p.W * n, WB = job.WB, nb = (size_t)job.WR * p.B;
+    if (o.sorted) FK_HIP(ctx, hipMemcpy(o.sorted, job.sorted, Wn * 4, hipMemcpyDeviceToHost));
+    if (o.totals) FK_HIP(ctx, hipMemcpy(o.totals, job.totals, WB * 4, hipMemcpyDeviceToHost));
+    if (o.starts) FK_HIP(ctx, hipMemcpy(o.starts, job.starts, WB * 4, hipMemcpyDeviceToHost));
+    if (o.perm) FK_HIP(ctx, hipMemcpy(o.perm, job.perm, (merged ? 2 * (size_t)p.B : WB) * 4, hipMemcpyDeviceToHost));
+    MsmDyn h{};
+    FK_HIP(ctx, hipMemcpy(&h, job.dyn, sizeof h, hipMemcpyDeviceToHost));
+    if (o.dyn) *o.dyn = fk_msm_dyn_info{h.cap, h.n_over, h.seg, h.n_tasks, h.n_obs, h.error, (uint64_t)h.adds};
+    const size_t n_tasks = std::min<size_t>(h.n_tasks, job.max_tasks), n_obs = std::min<size_t>(h.n_obs, OVER_MAX);
+    if (o.tasks && std::min(n_tasks, o.tasks_cap)) FK_HIP(ctx, hipMemcpy(o.tasks, job.tasks, std::min(n_tasks, o.tasks_cap) * sizeof(Task), hipMemcpyDeviceToHost));
+    if (o.obs && std::min(n_obs, o.obs_cap)) FK_HIP(ctx, hipMemcpy(o.obs, job.obs, std::min(n_obs, o.obs_cap) * sizeof(OverBucket), hipMemcpyDeviceToHost));
+    // ---- the accumulation
+    FK_TRY(queue_accumulate<F>(job));
+    FK_HIP(ctx, hipStreamSynchronize(ln.st));
+    if (o.buckets_acc && nb <= o.buckets_cap) FK_HIP(ctx, hipMemcpy(o.buckets_acc, bucket_buf(job), nb * sizeof(Xyzz<F>), hipMemcpyDeviceToHost));
+    // ---- the tail: oversized buckets, bucket reduction, fold, download of the window sums
+    FK_TRY(queue_tail<F>(job));
+    FK_HIP(ctx, hipStreamSynchronize(ln.st));
+    if (o.partials && std::min(n_tasks, o.partials_cap))
+        FK_HIP(ctx, hipMemcpy(o.partials, ln.partials.as<Xyzz<F>>(), std::min(n_tasks, o.partials_cap) * sizeof(Xyzz<F>), hipMemcpyDeviceToHost));
+    if (o.buckets && nb <= o.buckets_cap) FK_HIP(ctx, hipMemcpy(o.buckets, bucket_buf(job), nb * sizeof(Xyzz<F>), hipMemcpyDeviceToHost));
+    if (o.winparts) FK_HIP(ctx, hipMemcpy(o.winparts, job.winparts, (size_t)job.WR * p.nblk * sizeof(Xyzz<F>), hipMemcpyDeviceToHost));
+    if (o.folded) FK_HIP(ctx, hipMemcpy(o.folded, job.winparts + (size_t)job.WR * p.nblk, (size_t)job.WR * sizeof(Xyzz<F>), hipMemcpyDeviceToHost));
+    // ---- the host's Horner: the record is claimed as msm_begin claims it, msm_end releases it whatever it returns
+    tl.active = true; tl.cb = p.cb; tl.wide = p.wide; tl.W = job.WR; tl.nblk = 1;
+    Xyzz<F> res;
+    FK_TRY(msm_end<F>(ctx, ti, &res));
+    if (o.result) memcpy(o.result, &res, sizeof res);
+    return FK_OK;
+}
+
 // ------------------------------------------------------------------------------------------ fixed-base precomputation of a key
 // name: the key array (for the message); require: FK_MSM_PRECOMP=require -- fail instead of falling back when HBM is short
 template <class F>
@@ -1567,14 +1655,7 @@ static int precompute_levels(fk_ctx *ctx, const Affine<F> *d_bases, size_t n, Ke
         ctx->err += (ctx->err.empty() ? "warning: " : "; ") + std::string(msg) + " -- that array takes the slower W-bucket-set path";
         return FK_OK;
     }
-    const Affine<F> *prev = d_bases;
-    for (uint32_t w = 1; w < p.W; w++) {
-        Affine<F> *cur = (Affine<F> *)lev + (size_t)(w - 1) * n;
-        const uint32_t bits = p.cb + ((w - 1) < p.wide ? 1 : 0);       // width of window w-1
-        constexpr int NB = sizeof(F) == sizeof(Fq) ? 4 : 2;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(msm_level_kernel<F, NB>), dim3((unsigned)(((n + NB - 1) / NB + 255) / 256)), dim3(256), 0, ctx->stream, prev, n, bits, cur);
-        prev = cur;
-    }
+    queue_levels(ctx, d_bases, n, p, (Affine<F> *)lev);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipFree(lev); FK_SET_ERR(ctx, FK_ERR_HIP, "msm: level precomputation failed"); }
     out->lev = lev; out->n = n; out->cb = p.cb; out->wide = p.wide; out->W = p.W;
     return FK_OK;
@@ -2005,4 +2086,13 @@ int fk_msm_front_dump(fk_ctx *ctx, const void *d_scalars, size_t n, int merged, 
     if (n && (!d_scalars || !digits || !sorted || !totals || !starts || !perm || !dyn || (!tasks && tasks_cap) || (!obs && obs_cap))) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
     FK_HIP(ctx, hipSetDevice(ctx->device));
     return fk::msm_front_dump(ctx, (const fk::Fr *)d_scalars, n, merged != 0, digits, sorted, totals, starts, perm, dyn, tasks, tasks_cap, obs, obs_cap);
+}); }
+
+int fk_msm_back_dump(fk_ctx *ctx, int g2, const void *d_bases, const void *d_scalars, size_t n, int merged, const fk_msm_back_out *out) { return fk_guard(ctx, [&]() -> int {
+    if (!ctx) return FK_ERR_BAD_ARG;
+    if (n && (!d_bases || !d_scalars || !out)) FK_SET_ERR(ctx, FK_ERR_BAD_ARG, "null argument");
+    if (n == 0) return FK_OK;
+    FK_HIP(ctx, hipSetDevice(ctx->device));
+    if (g2) return fk::msm_back_dump<fk::Fq2>(ctx, (const fk::G2Affine *)d_bases, (const fk::Fr *)d_scalars, n, merged != 0, *out);
+    return fk::msm_back_dump<fk::Fq>(ctx, (const fk::G1Affine *)d_bases, (const fk::Fr *)d_scalars, n, merged != 0, *out);
 }); }

@@ -53,6 +53,30 @@ int fk_r1cs_plan_host(const fk_r1cs *cs, uint32_t copies, const uint32_t *a_cidx
  * own sort), queries seen, bytes of HBM the arrays and their levels occupy. */
 int fk_key_a_pad_info(const fk_key *key, uint64_t out[6]);
 
+/* The back of one multiplication, stage by stage (csrc/msm.hip; tests/test_gpu_msm_back.py): one whole multiplication over n device-resident
+ * bases (G1Affine, g2 != 0: G2Affine) and Montgomery scalars under the context's window bits, queued by the product's own host code
+ * (msm_reserve, queue_sort, queue_size_order, queue_accumulate, queue_tail, msm_end) on the next lane in turn, with the lane synchronised
+ * between the pieces so that what every kernel left can be copied out.  merged != 0: the one-bucket-set form; the levels of the bases are
+ * built here by the loop a key's are built by, and freed again.  The caller allocates the arrays of `out`; any may be NULL (not wanted).
+ * With p = fk_msm_plan(n, window bits, merged), WR = merged ? 1 : p.W bucket sets of p.B buckets, points as the device holds them (Xyzz:
+ * x, y, zz, zzz Montgomery limb images, 4 x 32 bytes in G1, 4 x 64 in G2; zz = 0: infinity):
+ *   sorted p.W * n, starts / totals p.W * p.B, perm p.W * p.B (merged: perm[p.B], then the merged lengths mt[p.B]), dyn, tasks (2 words
+ *   each, at most tasks_cap), obs (3 words each, at most obs_cap): as fk_msm_front_dump gives them;
+ *   buckets_acc: the WR * p.B buckets behind the accumulation; buckets: the same behind msm_overflow_fold_kernel -- both only when
+ *   WR * p.B <= buckets_cap; partials: dyn.n_tasks points (at most partials_cap); winparts: WR * p.nblk points; folded: WR points;
+ *   result: the point msm_end returns; levels (merged): (p.W - 1) * n affine points, level w at (w - 1) * n.
+ * Refused while a proof holds the lanes; the lane forgets the sort, no tail record stays active.  n = 0: FK_OK, nothing written. */
+typedef struct {
+    uint32_t *sorted, *starts, *totals, *perm;
+    fk_msm_dyn_info *dyn;
+    uint32_t *tasks; size_t tasks_cap;
+    uint32_t *obs; size_t obs_cap;
+    void *buckets_acc, *buckets; size_t buckets_cap;
+    void *partials; size_t partials_cap;
+    void *winparts, *folded, *result, *levels;
+} fk_msm_back_out;
+int fk_msm_back_dump(fk_ctx *ctx, int g2, const void *d_bases, const void *d_scalars, size_t n, int merged, const fk_msm_back_out *out);
+
 #ifdef __cplusplus
 }
 #endif
